@@ -18,6 +18,12 @@ table in HBM before the timed region; nothing copied back inside it).
           fills enqueued back to back give `pipelined_ms_per_fill`, reported beside
           it; fast-needleman-wunsch_amd/nw_bands.py, DESIGN.md "Multi-GPU".
 
+A plain run sets up, warms up, times the steps of `value` and prints the line.
+--full adds what else the bench reports (N = 1: the config-5 Smith-Waterman
+sub-measurement and the CPU baseline; N > 1: the `alt_partitions` legs and the CPU
+baseline).  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (dump_table), the same cells on every run.
+
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for field meanings).
 """
 from __future__ import annotations
@@ -57,8 +63,8 @@ def parse():
                     help="N>1: the partition reported as `value`: row bands (mpi-horz, BASELINE "
                          "config 4; default) or column bands (mpi-vert)")
     ap.add_argument("--alt-partition", choices=["rows", "cols", "none"], default=None,
-                    help="N>1: the alternate legs (`alt_partitions`; default: contiguous row bands "
-                         "and column bands)")
+                    help="N>1: the alternate legs (`alt_partitions`; default: none, with --full "
+                         "contiguous row bands and column bands)")
     ap.add_argument("--band-blocks", type=int, default=1,
                     help="N>1 row bands: blocks of rows per GPU, dealt round robin (1 = contiguous "
                          "mpi-horz bands; the block-cyclic alternate leg uses 2)")
@@ -91,7 +97,22 @@ def parse():
     ap.add_argument("--no-config5", action="store_true",
                     help="N=1: skip the config-5 (Smith-Waterman 64k + traceback) sub-measurement")
     ap.add_argument("--cpu-n", type=int, default=32768, help="CPU baseline sample side")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the config-5 (Smith-Waterman) "
+                         "sub-measurement and the CPU baseline (N=1), the alternate partitions and the CPU "
+                         "baseline (N>1); without it only the timed steps of `value` run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (score, border "
+                         "row / column and a fixed seeded sample of the table; the SW alignment for "
+                         "--workload sw) as DIR/<name>.npy in float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run measures `value` only; what else the bench reports runs under --full
+        args.no_config5 = args.no_cpu_baseline = True
+        if args.alt_partition is None:
+            args.alt_partition = "none"
     # per-workload defaults; values the user passed are never rewritten
     if args.n is None:
         args.n = 65536 if args.workload == "sw" else 262144
@@ -196,6 +217,50 @@ def pmc_traffic(workload: str, kernel: str):
                                            f"kernel {e.get('kernel_name', '?')}").strip()
 
 
+DUMP_SEED, DUMP_CELLS, DUMP_CELL_ROWS, DUMP_ROWS = 20240, 1 << 20, 64, 4
+
+
+def _save(dirname: str, name: str, a) -> None:
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def dump_indices(n1: int, n2: int):
+    """The table cells --dump-outputs samples, a function of the table size alone:
+    (rows, cell_rows, cell_cols) = the DUMP_ROWS rows dumped whole (sorted), and the
+    DUMP_CELL_ROWS rows with, for each, the columns of its sampled cells
+    (cell_cols[k] belongs to cell_rows[k]; up to DUMP_CELLS cells in all)."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.sort(rng.choice(n2 + 1, size=min(DUMP_ROWS, n2 + 1), replace=False))
+    per_row = min(n1 + 1, DUMP_CELLS // DUMP_CELL_ROWS)
+    cell_rows = rng.integers(0, n2 + 1, DUMP_CELL_ROWS)
+    cell_cols = rng.integers(0, n1 + 1, (DUMP_CELL_ROWS, per_row))
+    return rows, cell_rows, cell_cols
+
+
+def dump_table(dirname: str, tab, n1: int, n2: int) -> None:
+    """--dump-outputs: what a caller of the fill receives, the (n2+1) x (n1+1) table in
+    `tab`, as float64 .npy files (exact: the cells are int32): score.npy (the corner),
+    last_row.npy, last_col.npy, sample_rows.npy (whole rows) and sample_cells.npy
+    (single cells), rows and cells as dump_indices draws them with the fixed seed
+    DUMP_SEED, so two builds dump the same cells.  About 20 MB at 262144 x 262144."""
+    import numpy as np
+    import torch
+    rows, cell_rows, cell_cols = dump_indices(n1, n2)
+    cells = []
+    for r, cols in zip(cell_rows, cell_cols):
+        # (one row at a time: every index stays inside one row of the 275 GB table)
+        ci = torch.from_numpy(cols).to(tab.device)
+        cells.append(tab[int(r), :n1 + 1].index_select(0, ci).cpu().numpy())
+    _save(dirname, "score", [int(tab[n2, n1].item())])
+    _save(dirname, "last_row", tab[n2, :n1 + 1].cpu().numpy())
+    _save(dirname, "last_col", tab[:n2 + 1, n1].cpu().numpy())
+    _save(dirname, "sample_rows", np.stack([tab[int(r), :n1 + 1].cpu().numpy() for r in rows]))
+    _save(dirname, "sample_cells", np.stack(cells))
+
+
 def run_single(args):
     import torch
     import nwhip
@@ -228,6 +293,8 @@ def run_single(args):
     if status != 0:
         raise RuntimeError(f"fill reported status {status} ({nwhip.strerror(status)})")
     kms = [e0.elapsed_time(e1) for e0, e1 in evs]
+    if args.dump_outputs:
+        dump_table(args.dump_outputs, tab, n, n)  # (the last timed fill's table)
     shape = ctx.fill(s1, s2, tab, scheme, **kw)  # (one more fill, untimed: what ran)
     score = int(tab[n, n].item())
     want = golden_score(n, scheme)
@@ -278,7 +345,7 @@ def run_single(args):
 
 
 def measure_sw(n: int, scheme, steps: int, warmup: int, substrips: int = 0, strip_waves: int = 0,
-               kernel: int = 0) -> dict:
+               kernel: int = 0, dump: str | None = None) -> dict:
     """BASELINE config 5: Smith-Waterman fill + best cell + on-device traceback of
     the n x n synthetic pair (a step = all three), checked against
     tests/golden/sw_golden.json (the build's CPU restatement: the reference has no
@@ -311,6 +378,10 @@ def measure_sw(n: int, scheme, steps: int, warmup: int, substrips: int = 0, stri
         tbs.append(al.traceback_ms)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    if dump:  # the last timed step's table, alignment ends and edit script
+        dump_table(dump, tab, n, n)
+        _save(dump, "alignment", [al.score, al.end_i, al.end_j, al.begin_i, al.begin_j, al.n_ops])
+        _save(dump, "ops", ops)
     gpath = os.path.join(ROOT, "tests", "golden", "sw_golden.json")
     g = json.load(open(gpath))["synth"].get(f"{n}:{','.join(map(str, scheme))}") if os.path.exists(gpath) else None
     ok = None
@@ -341,7 +412,8 @@ def run_sw(args):
     """--workload sw: BASELINE config 5 as the line itself (measure_sw)."""
     import nwhip
     scheme = tuple(int(x) for x in args.scheme.split(","))
-    m = measure_sw(args.n, scheme, args.steps, args.warmup, args.substrips, args.strip_waves, args.kernel)
+    m = measure_sw(args.n, scheme, args.steps, args.warmup, args.substrips, args.strip_waves, args.kernel,
+                   dump=args.dump_outputs)
     out = {"metric": "GCUPS (DP cell updates/s) on NxN Smith-Waterman fill + on-device traceback",
            "value": m["value"], "unit": "GCUPS", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": m["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -412,6 +484,8 @@ def main():
         return
     import torch
     plan, why = launch_plan(args.gpus, os.environ.get("WORLD_SIZE"), torch.cuda.device_count(), args.share_gpu)
+    if plan != "single" and args.dump_outputs:
+        plan, why = "refuse", "--dump-outputs is implemented for --gpus 1 only"
     if plan == "refuse":
         print(f"bench.py: refusing to run: {why}", file=sys.stderr, flush=True)
         sys.exit(2)

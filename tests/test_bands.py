@@ -233,7 +233,7 @@ def test_two_process_bands_shared_gpu(torch_gpu, kernel, blocks, sweep):
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
            "--share-gpu", "--partition", "rows", "--band-rows", str(rows), "--band-blocks", str(blocks),
            "--band-cols", str(n1), "--col-width", str(width), "--col-rows", str(crows),
-           "--kernel", str(kernel), "--band-sweep", sweep, "--no-cpu-baseline"]
+           "--kernel", str(kernel), "--band-sweep", sweep, "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]

@@ -13,7 +13,7 @@ OUT=$R/$1
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp || exit 1
-B="python3 $R/bench.py --steps 10 --warmup 3"
+B="python3 $R/bench.py --steps 10 --warmup 3 --full"
 timeout -k 10 400 $B > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 11
 for pass in "kt:--kernel-trace --stats" "w:--pmc WRITE_SIZE" "f:--pmc FETCH_SIZE"; do
   n=${pass%%:*}; a=${pass#*:}

@@ -12,11 +12,11 @@ ARGS="$@"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp || exit 1
-timeout -k 10 900 python3 "$R/bench.py" $ARGS > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 11
+timeout -k 10 900 python3 "$R/bench.py" $ARGS --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 11
 timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o kt -- \
-    python3 "$R/bench.py" $ARGS --no-cpu-baseline > "$OUT/kt.log" 2>&1 || exit 12
+    python3 "$R/bench.py" $ARGS --full --no-cpu-baseline > "$OUT/kt.log" 2>&1 || exit 12
 timeout -k 10 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_w" -o pmc -- \
-    python3 "$R/bench.py" $ARGS --no-cpu-baseline > "$OUT/pmc_w.log" 2>&1 || exit 13
+    python3 "$R/bench.py" $ARGS --full --no-cpu-baseline > "$OUT/pmc_w.log" 2>&1 || exit 13
 timeout -k 10 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_f" -o pmc -- \
-    python3 "$R/bench.py" $ARGS --no-cpu-baseline > "$OUT/pmc_f.log" 2>&1 || exit 14
+    python3 "$R/bench.py" $ARGS --full --no-cpu-baseline > "$OUT/pmc_f.log" 2>&1 || exit 14
 echo ok > "$OUT/done"
