@@ -60,3 +60,45 @@ void nw_synth_bdna(uint64_t seed, int64_t n, int8_t *out) {
 }
 
 }  // extern "C"
+
+// Walk alignment ops from (begin_i, begin_j); f(k, op, i, j) sees the cell BEFORE
+// the move, i.e. the characters s2[i] / s1[j] that the move consumes.
+template <typename F>
+static int walk_ops(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t i, int64_t j,
+                    const uint8_t *ops, int64_t n_ops, F &&f) {
+    if (n1 < 0 || n2 < 0 || n_ops < 0 || i < 0 || j < 0 || i > n2 || j > n1) return NW_ERR_ARG;
+    if ((n_ops > 0 && !ops) || (n1 > 0 && !s1) || (n2 > 0 && !s2)) return NW_ERR_ARG;
+    for (int64_t k = 0; k < n_ops; ++k) {
+        const uint8_t op = ops[k];
+        if (op > 2) return NW_ERR_ARG;
+        if ((op != 2 && i >= n2) || (op != 1 && j >= n1)) return NW_ERR_ARG;
+        f(k, op, i, j);
+        i += op != 2;
+        j += op != 1;
+    }
+    return NW_OK;
+}
+
+extern "C" {
+
+int nw_ops_expand(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t begin_i, int64_t begin_j,
+                  const uint8_t *ops, int64_t n_ops, int8_t *row1, int8_t *row2) {
+    if (n_ops > 0 && (!row1 || !row2)) return NW_ERR_ARG;
+    return walk_ops(s1, n1, s2, n2, begin_i, begin_j, ops, n_ops, [&](int64_t k, uint8_t op, int64_t i, int64_t j) {
+        row1[k] = op != 1 ? s1[j] : 0;
+        row2[k] = op != 2 ? s2[i] : 0;
+    });
+}
+
+int nw_ops_score(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t begin_i, int64_t begin_j,
+                 const uint8_t *ops, int64_t n_ops, const nw_params *p, int64_t *score) {
+    if (!p || !score) return NW_ERR_ARG;
+    int64_t sum = 0;
+    const int st = walk_ops(s1, n1, s2, n2, begin_i, begin_j, ops, n_ops, [&](int64_t, uint8_t op, int64_t i, int64_t j) {
+        sum += op != 0 ? p->gap : s1[j] == s2[i] ? p->match : p->mismatch;
+    });
+    if (st == NW_OK) *score = sum;
+    return st;
+}
+
+}  // extern "C"

@@ -224,6 +224,30 @@ bool valid_params(const nw_params *p) {
     return std::abs(p->match) < lim && std::abs(p->mismatch) < lim && std::abs(p->gap) < lim;
 }
 
+// Arguments of nw_traceback / nw_align that need no device to judge; on NW_OK the
+// window geometry (defaults applied) and the aim.
+int tb_args(int64_t n1, int64_t n2, const nw_params *p, const nw_tb_opts *o, const uint8_t *ops, int64_t ops_cap,
+            const nw_alignment *out, int32_t *band, int32_t *maxwin, int32_t *aim) {
+    if (!out || n1 < 0 || n2 < 0 || n1 >= INT32_MAX || n2 >= INT32_MAX) return NW_ERR_ARG;
+    if (!valid_params(p) || p->mode != NW_MODE_NW) return NW_ERR_ARG;
+    // the table must hold a fill: no scratch-tile stores, no probes
+    if ((p->flags & (NW_FLAG_TIMING_ONLY | NW_FLAG_DEBUG_DRAIN | NW_FLAG_DEBUG_NO_STORE | NW_FLAG_DEBUG_NO_CHAIN |
+                     NW_FLAG_DEBUG_STAGGER)) != 0)
+        return NW_ERR_ARG;
+    if (ops_cap < n1 + n2 || (n1 + n2 > 0 && !ops)) return NW_ERR_ARG;
+    *band = nw::kTbBandDefault;
+    *maxwin = nw::kTbMaxWinDefault;
+    *aim = 1;
+    if (o) {
+        if (o->band < 0 || o->band > 256 || o->max_windows < 0 || (o->flags & ~NW_TB_NO_AIM) != 0 || o->reserved != 0)
+            return NW_ERR_ARG;
+        if (o->band > 0) *band = o->band;
+        if (o->max_windows > 0) *maxwin = o->max_windows;
+        *aim = (o->flags & NW_TB_NO_AIM) ? 0 : 1;
+    }
+    return NW_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -248,6 +272,7 @@ const char *nw_strerror(int status) {
         case NW_ERR_TIMEOUT: return "in-kernel hand-off watchdog expired";
         case NW_ERR_NODEVICE: return "no gfx950 device";
         case NW_ERR_UNSUPPORTED: return "unsupported";
+        case NW_ERR_TABLE: return "traceback met a cell no move reproduces (not a table of these parameters)";
         default: return "unknown status";
     }
 }
@@ -1063,6 +1088,57 @@ int nw_sw_traceback(nw_ctx *c, const int8_t *d_s1, int64_t n1, const int8_t *d_s
     return NW_OK;
 }
 
+int nw_traceback(nw_ctx *c, const int8_t *d_s1, int64_t n1, const int8_t *d_s2, int64_t n2, const nw_params *p,
+                 const int32_t *d_t, int64_t pitch, const nw_tb_opts *o, void *stream, uint8_t *host_ops,
+                 int64_t ops_cap, nw_alignment *out, nw_tb_stats *stats) {
+    int32_t band = 0, maxwin = 0, aim = 0;
+    int st = tb_args(n1, n2, p, o, host_ops, ops_cap, out, &band, &maxwin, &aim);
+    if (st != NW_OK) return st;
+    if (!c || !d_t || pitch < n1 + 1 || (n1 > 0 && !d_s1) || (n2 > 0 && !d_s2)) return NW_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    NW_HIP_TRY(hipSetDevice(c->device));
+    const size_t need = (size_t)std::max<int64_t>(n1 + n2, 1);
+    if ((st = grow((void **)&c->ops, &c->ops_cap, need)) != NW_OK) return st;
+    maxwin = (int32_t)std::min<int64_t>(maxwin, n2 / 64 + 1);
+    if ((st = grow((void **)&c->tbscratch, &c->tbscratch_cap, nw::sw_tb_scratch_bytes(maxwin, band))) != NW_OK)
+        return st;
+    // everything below is ordered on the caller's stream, after its fill
+    NW_HIP_TRY(hipEventRecord(c->ev0, s));
+    int64_t info[10];
+    const int he = nw::run_nw_traceback(d_t, pitch, n1, n2, (const uint8_t *)d_s1, (const uint8_t *)d_s2, p->match,
+                                        p->mismatch, p->gap, c->ops, n1 + n2, c->tbscratch, maxwin, band, aim, info,
+                                        stream);
+    if (he != hipSuccess) {
+        std::fprintf(stderr, "libnwhip: traceback failed: %s\n", hipGetErrorString((hipError_t)he));
+        return NW_ERR_HIP;
+    }
+    std::memset(out, 0, sizeof *out);
+    out->end_i = n2;
+    out->end_j = n1;
+    if (stats) {
+        stats->rounds = (int32_t)info[4];
+        stats->windows = (int32_t)info[5];
+        stats->band = band;
+        stats->max_windows = maxwin;
+        stats->tail_ops = info[6];
+    }
+    // a global path never has more than n1 + n2 ops: a full buffer (1) is a bad table too
+    const bool ok = info[3] == 0;
+    NW_HIP_TRY(hipMemcpyAsync(&out->score, d_t + n2 * pitch + n1, 4, hipMemcpyDeviceToHost, s));
+    if (ok && info[0] > 0) NW_HIP_TRY(hipMemcpyAsync(host_ops, c->ops, (size_t)info[0], hipMemcpyDeviceToHost, s));
+    NW_HIP_TRY(hipEventRecord(c->ev1, s));
+    NW_HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0.f;
+    NW_HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    out->traceback_ms = ms;
+    out->status = ok ? NW_OK : NW_ERR_TABLE;
+    if (!ok) return NW_ERR_TABLE;
+    out->n_ops = info[0];
+    // the kernels walk end -> begin; hand the ops over begin -> end
+    std::reverse(host_ops, host_ops + info[0]);
+    return NW_OK;
+}
+
 // ---- host-buffer entry points (the drop-in path) ----------------------------
 //
 // One HostPath per device, created on first use and kept: the context, the
@@ -1280,6 +1356,52 @@ int nw_sw_align(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, cons
     if (st == NW_OK) st = nw_fill_device(h.c, h.s1, n1, h.s2, n2, p, d_t, pitch, nullptr, &r);
     if (st == NW_OK) st = nw_sw_traceback(h.c, h.s1, n1, h.s2, n2, p, d_t, pitch, r.end_i, r.end_j, host_ops,
                                           ops_cap, out);
+    if (st == NW_OK) out->fill_ms = r.kernel_ms;
+    host_trim(h);
+    out->status = st;
+    return st;
+}
+
+int nw_align(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, const nw_params *p, const nw_tb_opts *o,
+             uint8_t *host_ops, int64_t ops_cap, nw_alignment *out, nw_tb_stats *stats) {
+    nw_params def;
+    if (!p) {
+        nw_params_default(&def);
+        p = &def;
+    }
+    int32_t band = 0, maxwin = 0, aim = 0;
+    int st = tb_args(n1, n2, p, o, host_ops, ops_cap, out, &band, &maxwin, &aim);
+    if (st != NW_OK) return st;
+    if ((n1 > 0 && !s1) || (n2 > 0 && !s2)) return NW_ERR_ARG;
+    int dev, ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return NW_ERR_NODEVICE;
+    if ((st = host_device(p, &dev)) != NW_OK) return st;
+    if (n1 == 0 || n2 == 0) {
+        // no table: the path runs along row 0 (lefts) or column 0 (ups)
+        const int64_t n = std::max(n1, n2);
+        std::memset(out, 0, sizeof *out);
+        if (n > 0) std::memset(host_ops, n2 > 0 ? 1 : 2, (size_t)n);
+        out->score = (int32_t)(p->gap * n);
+        out->end_i = n2;
+        out->end_j = n1;
+        out->n_ops = n;
+        if (stats) {
+            std::memset(stats, 0, sizeof *stats);
+            stats->band = band;
+            stats->max_windows = maxwin;
+            stats->tail_ops = n;
+        }
+        return NW_OK;
+    }
+    HostPath &h = g_host[dev];
+    std::lock_guard<std::mutex> lock(h.mu);
+    int32_t *d_t = nullptr;
+    int64_t pitch = 0;
+    nw_result r;
+    std::memset(&r, 0, sizeof r);
+    st = host_prepare(h, dev, s1, n1, s2, n2, &d_t, &pitch);
+    if (st == NW_OK) st = nw_fill_device(h.c, h.s1, n1, h.s2, n2, p, d_t, pitch, nullptr, &r);
+    if (st == NW_OK) st = nw_traceback(h.c, h.s1, n1, h.s2, n2, p, d_t, pitch, o, nullptr, host_ops, ops_cap, out, stats);
     if (st == NW_OK) out->fill_ms = r.kernel_ms;
     host_trim(h);
     out->status = st;

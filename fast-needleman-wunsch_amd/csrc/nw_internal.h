@@ -132,7 +132,14 @@ size_t sw_tb_scratch_bytes(int32_t maxwin, int32_t band);
 int run_sw_traceback(const int32_t *table, int64_t pitch, int64_t n1, const uint8_t *s1, const uint8_t *s2,
                      int32_t match, int32_t mismatch, int32_t gap, int64_t end_i, int64_t end_j, uint8_t *ops,
                      int64_t ops_cap, void *scratch, int32_t maxwin, int32_t band, int64_t *info, void *stream);
-constexpr int32_t kTbBandDefault = 256;    // band half-width of the traceback windows (profiles/r03s_tb_geometry.txt)
+// the same for a global (NW_MODE_NW) table, from (n2, n1) to (0, 0): rounds aimed
+// at (0, 0) unless aim = 0, the forced moves along row 0 / column 0 written by one
+// memset on `stream`; info as above ([3] = 2: a cell no move reproduces), [1..2] =
+// (0, 0) on success, [6] = ops of that boundary tail
+int run_nw_traceback(const int32_t *table, int64_t pitch, int64_t n1, int64_t n2, const uint8_t *s1,
+                     const uint8_t *s2, int32_t match, int32_t mismatch, int32_t gap, uint8_t *ops, int64_t ops_cap,
+                     void *scratch, int32_t maxwin, int32_t band, int32_t aim, int64_t *info, void *stream);
+constexpr int32_t kTbBandDefault = 256;   // band half-width of the traceback windows (profiles/r03s_tb_geometry.txt)
 constexpr int32_t kTbMaxWinDefault = 512;  // windows per round (64 rows each)
 
 // Launch helpers implemented in nw_fill.hip.  Return hipError_t as int.

@@ -9,7 +9,8 @@
 //   * traceback from it while t > 0, preferring diag > up > left -- the order in
 //     which serial.cpp:24-30 takes its maximum (a, then b, then c).
 // Both kernels are memory-latency work on a table already in HBM; neither is on
-// the fill's store path.
+// the fill's store path.  The traceback also walks global (Needleman-Wunsch)
+// tables from (n2, n1) to (0, 0) -- its second kind, below (nw_traceback).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -161,6 +162,16 @@ int launch_sw_fixup(int32_t *table, int64_t pitch, int64_t n1, int64_t n2, const
 //     writes the ops at its offset.
 // A path that drifts more than B columns off the round's diagonal costs another
 // round (re-centred at the cell where it left); run_sw_traceback loops rounds.
+//
+// The same windows serve two KINDS of table.  kTbLocal is the Smith-Waterman walk
+// above.  kTbGlobal walks a Needleman-Wunsch table from (n2, n1) to (0, 0): no
+// t > 0 test, the stop is the cell (0, 0) alone, and row 0 / column 0 force left /
+// up without reading the table.  A global path follows the line from the round's
+// start cell to (0, 0), not the slope-1 diagonal, so a global round is AIMED:
+// window k's column origin is dj minus the cumulative shift tb_shift(k), which
+// follows that line with a step of at most B / 2 columns per window; the chain
+// adds the step to the column it carries into the next window.  Local rounds pass
+// "no aim" and get a shift of 0 everywhere.
 constexpr int kTbR = 64;                     // rows per window
 constexpr int kTbBMax = 256;                 // band half-width B <= kTbBMax
 constexpr int kTbWMax = 2 * kTbBMax + 1;     // cells per window row, W = 2B + 1
@@ -172,6 +183,20 @@ enum : uint32_t { kXCont = 0, kXStop = 1, kXOut = 2, kXBad = 3 };
 // column entered in the next window; otherwise the cell where the walk ended)
 __device__ __forceinline__ uint32_t xrec(uint32_t kind, uint32_t cnt, uint32_t r, uint32_t x) {
     return kind | (cnt << 2) | (r << 12) | (x << 19);
+}
+
+enum : int { kTbLocal = 0, kTbGlobal = 1 };
+
+// Cumulative column shift c_k of window k in a round from (is, js), is >= 1, aimed
+// at (0, 0): the line's k * kTbR * (js - is) / is, or k * (B / 2) towards it when
+// the line moves more than B / 2 columns per window (c_0 = 0; a step c_{k+1} - c_k
+// never exceeds B / 2 either way).  aim = 0: no shift.
+__host__ __device__ __forceinline__ int64_t tb_shift(int64_t k, int64_t is, int64_t js, int32_t B, int32_t aim) {
+    if (!aim) return 0;
+    const int64_t num = js - is, lim = B / 2;
+    const int64_t mag = num < 0 ? -num : num;
+    if (kTbR * mag > lim * is) return (num < 0 ? -k : k) * lim;
+    return k * kTbR * num / is;
 }
 
 // One window's walk from entry x (row kTbR - 1) over its move codes cd[]: calls
@@ -194,17 +219,18 @@ __device__ __forceinline__ uint32_t tb_walk(const uint8_t *cd, int W, int x, F &
     }
 }
 
+template <int KIND>
 __global__ __launch_bounds__(kTbThreads) void nw_tb_windows(const int32_t *__restrict__ table, int64_t pitch,
                                                             int64_t n1, const uint8_t *__restrict__ s1,
                                                             const uint8_t *__restrict__ s2, int32_t match,
                                                             int32_t mismatch, int32_t gap, int64_t is, int64_t js,
-                                                            int32_t B, uint8_t *__restrict__ codes,
+                                                            int32_t B, int32_t aim, uint8_t *__restrict__ codes,
                                                             uint32_t *__restrict__ exits) {
     __shared__ uint8_t cd[kTbR * kTbWMax];
     const int W = 2 * B + 1;
     const int k = blockIdx.x;
     const int64_t i0 = is - (int64_t)(k + 1) * kTbR + 1;
-    const int64_t dj = js - is + i0 - B;
+    const int64_t dj = js - is + i0 - B - tb_shift(k, is, js, B, aim);
     const int ncell = kTbR * W;
     uint8_t *gcd = codes + (int64_t)k * ncell;
 #pragma unroll 4
@@ -217,8 +243,19 @@ __global__ __launch_bounds__(kTbThreads) void nw_tb_windows(const int32_t *__res
         const int32_t *row = table + ic * pitch;
         const int32_t t = row[jc], td = row[jc - 1 - pitch], tu = row[jc - pitch], tl = row[jc - 1];
         const int32_t sc = s1[jc - 1] == s2[ic - 1] ? match : mismatch;
-        uint8_t c = kCStop;
-        if (in && t > 0) c = t == td + sc ? kCDiag : t == tu + gap ? kCUp : t == tl + gap ? kCLeft : kCBad;
+        const uint8_t mv = t == td + sc ? kCDiag : t == tu + gap ? kCUp : t == tl + gap ? kCLeft : kCBad;
+        uint8_t c;
+        if (KIND == kTbLocal) {
+            c = in && t > 0 ? mv : kCStop;
+        } else {
+            // row 0 / column 0 are forced (the loaded values are not theirs); cells
+            // outside the table are bad: a valid path never reaches them
+            c = in ? mv
+                   : i == 0 && j == 0 ? kCStop
+                   : i == 0 && j > 0 && j <= n1 ? kCLeft
+                   : j == 0 && i > 0 ? kCUp
+                                     : kCBad;
+        }
         cd[e] = c;
         gcd[e] = c;
     }
@@ -229,8 +266,11 @@ __global__ __launch_bounds__(kTbThreads) void nw_tb_windows(const int32_t *__res
 // ctl: [0] ops so far, [1] how the round ended (kXStop / kXCont|kXOut = restart /
 // kXBad / 4 = ops buffer too small), [2..3] the begin cell or the restart cell,
 // [4] windows holding ops this round.  wentry[k] = {entry x, ops offset}.
+// An aimed round (tb_shift) enters window k + 1 at the exit column plus the step
+// c_{k+1} - c_k; an entry outside [0, W) ends the round at that cell, like a move
+// out of the band.
 __global__ __launch_bounds__(1024) void nw_tb_chain(const uint32_t *__restrict__ exits, int32_t nwin, int32_t B,
-                                                    int64_t is, int64_t js, int64_t ops_cap,
+                                                    int32_t aim, int64_t is, int64_t js, int64_t ops_cap,
                                                     int64_t *__restrict__ wentry, int64_t *__restrict__ ctl) {
     __shared__ uint32_t ex[kChain * kTbWMax];
     __shared__ int64_t st[3];  // entry x, ops offset, done
@@ -255,10 +295,14 @@ __global__ __launch_bounds__(1024) void nw_tb_chain(const uint32_t *__restrict__
                 const uint32_t rec = ex[kk * W + x];
                 const uint32_t kind = rec & 3u, cnt = (rec >> 2) & 1023u, r = (rec >> 12) & 127u, xx = rec >> 19;
                 off += cnt;
+                const int64_t ck = tb_shift(k, is, js, B, aim);
                 x = (int)xx;
-                if (kind == kXCont && k + 1 < nwin) continue;
+                if (kind == kXCont && k + 1 < nwin) {
+                    x += (int)(tb_shift(k + 1, is, js, B, aim) - ck);
+                    if (x >= 0 && x < W) continue;
+                }
                 // the round ends in window k
-                const int64_t i0 = is - (int64_t)(k + 1) * kTbR + 1, dj = js - is + i0 - B;
+                const int64_t i0 = is - (int64_t)(k + 1) * kTbR + 1, dj = js - is + i0 - B - ck;
                 ctl[1] = off > ops_cap ? 4 : (int64_t)kind;
                 ctl[2] = kind == kXCont ? i0 - 1 : i0 + r;
                 ctl[3] = kind == kXCont ? dj - 1 + xx : dj + r + xx;
@@ -302,9 +346,20 @@ size_t sw_tb_scratch_bytes(int32_t maxwin, int32_t band) {
     return 64 + (size_t)maxwin * (16 + 4 * W + kTbR * W);
 }
 
-int run_sw_traceback(const int32_t *table, int64_t pitch, int64_t n1, const uint8_t *s1, const uint8_t *s2,
-                     int32_t match, int32_t mismatch, int32_t gap, int64_t end_i, int64_t end_j, uint8_t *ops,
-                     int64_t ops_cap, void *scratch, int32_t maxwin, int32_t band, int64_t *info, void *stream) {
+// Windows worth launching in an aimed round whose line outruns the B / 2 step: the
+// path drifts (line step - B / 2) columns per window off the windows' centre and
+// leaves the band after about B / drift of them; later windows would be unused.
+static int32_t tb_steep_cap(int64_t is, int64_t js, int32_t B) {
+    const int64_t num = js - is, mag = num < 0 ? -num : num, lim = B / 2;
+    const int64_t drift = (kTbR * mag - lim * is) / is;
+    return drift <= 0 ? INT32_MAX : (int32_t)std::min<int64_t>(B / drift + 2, INT32_MAX);
+}
+
+template <int KIND>
+static int run_traceback(const int32_t *table, int64_t pitch, int64_t n1, const uint8_t *s1, const uint8_t *s2,
+                         int32_t match, int32_t mismatch, int32_t gap, int64_t end_i, int64_t end_j, uint8_t *ops,
+                         int64_t ops_cap, void *scratch, int32_t maxwin, int32_t band, int32_t aim, int64_t *info,
+                         void *stream) {
     hipStream_t s = (hipStream_t)stream;
     for (int q = 0; q < 10; ++q) info[q] = 0;
     if (band < 1 || band > kTbBMax || maxwin < 1) return (int)hipErrorInvalidValue;
@@ -322,10 +377,12 @@ int run_sw_traceback(const int32_t *table, int64_t pitch, int64_t n1, const uint
             info[2] = cj;
             break;
         }
-        const int32_t nwin = (int32_t)std::min<int64_t>((ci + kTbR) / kTbR, maxwin);
-        hipLaunchKernelGGL(nw_tb_windows, dim3((unsigned)nwin), dim3(kTbThreads), 0, s, table, pitch, n1, s1, s2,
-                           match, mismatch, gap, ci, cj, band, codes, exits);
-        hipLaunchKernelGGL(nw_tb_chain, dim3(1), dim3(1024), 0, s, exits, nwin, band, ci, cj, ops_cap, wentry, ctl);
+        int32_t nwin = (int32_t)std::min<int64_t>((ci + kTbR) / kTbR, maxwin);
+        if (aim) nwin = std::min(nwin, tb_steep_cap(ci, cj, band));
+        hipLaunchKernelGGL(nw_tb_windows<KIND>, dim3((unsigned)nwin), dim3(kTbThreads), 0, s, table, pitch, n1, s1,
+                           s2, match, mismatch, gap, ci, cj, band, aim, codes, exits);
+        hipLaunchKernelGGL(nw_tb_chain, dim3(1), dim3(1024), 0, s, exits, nwin, band, aim, ci, cj, ops_cap, wentry,
+                           ctl);
         hipLaunchKernelGGL(nw_tb_emit, dim3((unsigned)nwin), dim3(256), 0, s, codes, band, wentry, ctl, ops);
         if ((e = hipGetLastError()) != hipSuccess) return (int)e;
         if ((e = hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
@@ -347,7 +404,36 @@ int run_sw_traceback(const int32_t *table, int64_t pitch, int64_t n1, const uint
         ci = h[2];  // kXCont past the round's last window, or kXOut: re-centre there
         cj = h[3];
     }
+    if (KIND == kTbGlobal && info[3] == 0 && (info[1] > 0 || info[2] > 0)) {
+        // on row 0 / column 0 the rest of the path is forced: info[2] lefts or info[1] ups
+        const int64_t tail = info[1] > 0 ? info[1] : info[2];
+        if (info[1] < 0 || info[2] < 0 || (info[1] > 0 && info[2] > 0)) {
+            info[3] = 2;  // (unreachable on a table of these parameters)
+        } else if (info[0] + tail > ops_cap) {
+            info[3] = 1;
+        } else {
+            if ((e = hipMemsetAsync(ops + info[0], info[1] > 0 ? 1 : 2, (size_t)tail, s)) != hipSuccess)
+                return (int)e;
+            info[0] += tail;
+            info[6] = tail;
+            info[1] = info[2] = 0;
+        }
+    }
     return (int)hipSuccess;
+}
+
+int run_sw_traceback(const int32_t *table, int64_t pitch, int64_t n1, const uint8_t *s1, const uint8_t *s2,
+                     int32_t match, int32_t mismatch, int32_t gap, int64_t end_i, int64_t end_j, uint8_t *ops,
+                     int64_t ops_cap, void *scratch, int32_t maxwin, int32_t band, int64_t *info, void *stream) {
+    return run_traceback<kTbLocal>(table, pitch, n1, s1, s2, match, mismatch, gap, end_i, end_j, ops, ops_cap, scratch,
+                                   maxwin, band, 0, info, stream);
+}
+
+int run_nw_traceback(const int32_t *table, int64_t pitch, int64_t n1, int64_t n2, const uint8_t *s1,
+                     const uint8_t *s2, int32_t match, int32_t mismatch, int32_t gap, uint8_t *ops, int64_t ops_cap,
+                     void *scratch, int32_t maxwin, int32_t band, int32_t aim, int64_t *info, void *stream) {
+    return run_traceback<kTbGlobal>(table, pitch, n1, s1, s2, match, mismatch, gap, n2, n1, ops, ops_cap, scratch,
+                                    maxwin, band, aim, info, stream);
 }
 
 }  // namespace nw

@@ -22,6 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NWHIP_LIB") or os.path.join(HERE, "build", "libnwhip.so")
 
 NW_OK, NW_ERR_ARG, NW_ERR_HIP, NW_ERR_OOM, NW_ERR_TIMEOUT, NW_ERR_NODEVICE, NW_ERR_UNSUPPORTED = range(7)
+NW_ERR_TABLE = 7  # traceback: a cell no move reproduces (not a table of these parameters)
 MODE_NW, MODE_SW = 0, 1  # nw_params.mode: global (the reference fills) / Smith-Waterman local
 # nw_params.kernel: auto / anti-diagonal strips (nw_fill.hip) / row-scan panels (nw_rows.hip)
 KERNEL_AUTO, KERNEL_STRIPS, KERNEL_PANELS = 0, 1, 2
@@ -36,7 +37,8 @@ EXPORTS = ["nw_params_default", "nw_strerror", "nw_version", "nw_fill", "nw_tabl
            "nw_debug_trace_words", "nw_colband_layout", "nw_feed_bytes", "nw_feed_alloc",
            "nw_fill_colband_async", "nw_link_alloc", "nw_link_wait_async", "nw_link_signal_async",
            "nw_link_status", "nw_host_warmup", "nw_host_release", "nw_halo_alloc_regions",
-           "nw_fill_band_cycle_async", "nw_fill_tband_async", "nw_link_wait_ctx_async", "nw_debug_failure"]
+           "nw_fill_band_cycle_async", "nw_fill_tband_async", "nw_link_wait_ctx_async", "nw_debug_failure",
+           "nw_traceback", "nw_align", "nw_ops_expand", "nw_ops_score"]
 IPC_HANDLE_BYTES = 64
 
 
@@ -62,6 +64,21 @@ class NwAlignment(ctypes.Structure):
     _fields_ = [("score", ctypes.c_int32), ("status", ctypes.c_int32), ("begin_i", ctypes.c_int64),
                 ("begin_j", ctypes.c_int64), ("end_i", ctypes.c_int64), ("end_j", ctypes.c_int64),
                 ("n_ops", ctypes.c_int64), ("fill_ms", ctypes.c_double), ("traceback_ms", ctypes.c_double)]
+
+
+class NwTbOpts(ctypes.Structure):
+    """nw_tb_opts (include/nw_hip.h): window geometry of the global traceback (0 = default)."""
+    _fields_ = [("band", ctypes.c_int32), ("max_windows", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class NwTbStats(ctypes.Structure):
+    """nw_tb_stats (include/nw_hip.h): what a global traceback ran."""
+    _fields_ = [("rounds", ctypes.c_int32), ("windows", ctypes.c_int32), ("band", ctypes.c_int32),
+                ("max_windows", ctypes.c_int32), ("tail_ops", ctypes.c_int64)]
+
+
+TB_NO_AIM = 1  # nw_tb_opts.flags NW_TB_NO_AIM: diagonal rounds instead of rounds aimed at (0, 0)
 
 
 class NwBand(ctypes.Structure):
@@ -135,6 +152,17 @@ def lib() -> ctypes.CDLL:
                                   ctypes.c_int64, ctypes.POINTER(NwParams), ctypes.c_void_p, ctypes.c_int64,
                                   ctypes.c_int64, ctypes.c_int64, _u8p, ctypes.c_int64,
                                   ctypes.POINTER(NwAlignment)]
+    L.nw_traceback.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                               ctypes.POINTER(NwParams), ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(NwTbOpts),
+                               ctypes.c_void_p, _u8p, ctypes.c_int64, ctypes.POINTER(NwAlignment),
+                               ctypes.POINTER(NwTbStats)]
+    L.nw_align.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.POINTER(NwParams),
+                           ctypes.POINTER(NwTbOpts), _u8p, ctypes.c_int64, ctypes.POINTER(NwAlignment),
+                           ctypes.POINTER(NwTbStats)]
+    L.nw_ops_expand.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _u8p,
+                                ctypes.c_int64, _i8p, _i8p]
+    L.nw_ops_score.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _u8p,
+                               ctypes.c_int64, ctypes.POINTER(NwParams), ctypes.POINTER(ctypes.c_int64)]
     L.nw_table_pitch.argtypes = [ctypes.c_int64]
     L.nw_table_pitch.restype = ctypes.c_int64
     L.nw_table_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
@@ -265,6 +293,57 @@ def sw_align(s1, s2, scheme=(1, -1, -1), device: int = -1, substrips: int = 0, s
     if st != NW_OK:
         raise NwError(st, "nw_sw_align")
     return out, ops[:out.n_ops].copy()
+
+
+def tb_opts(band: int = 0, max_windows: int = 0, no_aim: bool = False) -> NwTbOpts:
+    return NwTbOpts(int(band), int(max_windows), TB_NO_AIM if no_aim else 0, 0)
+
+
+def align(s1, s2, scheme=(1, 0, -1), band: int = 0, max_windows: int = 0, no_aim: bool = False,
+          device: int = -1, substrips: int = 0, strip_waves: int = 0, kernel: int = KERNEL_AUTO):
+    """Global alignment on the device (nw_align): returns (NwAlignment, ops, NwTbStats),
+    ops a uint8 array in path order from (0, 0) to (n2, n1) (0 diag, 1 up, 2 left).
+    band / max_windows / no_aim: nw_tb_opts (0 = the defaults)."""
+    a, b = _seq(s1), _seq(s2)
+    ops = np.empty(max(a.size + b.size, 1), dtype=np.uint8)
+    out, stats = NwAlignment(), NwTbStats()
+    p = params(scheme, device=device, substrips=substrips, strip_waves=strip_waves, kernel=kernel)
+    o = tb_opts(band, max_windows, no_aim)
+    st = lib().nw_align(a.ctypes.data_as(_i8p), a.size, b.ctypes.data_as(_i8p), b.size, ctypes.byref(p),
+                        ctypes.byref(o), ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), a.size + b.size,
+                        ctypes.byref(out), ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_align")
+    return out, ops[:out.n_ops].copy(), stats
+
+
+def ops_expand(s1, s2, ops, begin=(0, 0)):
+    """The two gapped rows of an alignment (nw_ops_expand): (row1 from s1, row2 from s2),
+    int8 arrays of len(ops) with 0 = gap; `begin` = (begin_i, begin_j), (0, 0) for a
+    global alignment."""
+    a, b = _seq(s1), _seq(s2)
+    o = np.ascontiguousarray(np.asarray(ops, dtype=np.uint8))
+    r1, r2 = np.zeros(max(o.size, 1), np.int8), np.zeros(max(o.size, 1), np.int8)
+    st = lib().nw_ops_expand(a.ctypes.data_as(_i8p), a.size, b.ctypes.data_as(_i8p), b.size, int(begin[0]),
+                             int(begin[1]), o.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), o.size,
+                             r1.ctypes.data_as(_i8p), r2.ctypes.data_as(_i8p))
+    if st != NW_OK:
+        raise NwError(st, "nw_ops_expand")
+    return r1[:o.size], r2[:o.size]
+
+
+def ops_score(s1, s2, ops, scheme=(1, 0, -1), begin=(0, 0)) -> int:
+    """Sum of match / mismatch / gap along an alignment's ops (nw_ops_score)."""
+    a, b = _seq(s1), _seq(s2)
+    o = np.ascontiguousarray(np.asarray(ops, dtype=np.uint8))
+    p = params(scheme)
+    sc = ctypes.c_int64()
+    st = lib().nw_ops_score(a.ctypes.data_as(_i8p), a.size, b.ctypes.data_as(_i8p), b.size, int(begin[0]),
+                            int(begin[1]), o.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), o.size,
+                            ctypes.byref(p), ctypes.byref(sc))
+    if st != NW_OK:
+        raise NwError(st, "nw_ops_score")
+    return int(sc.value)
 
 
 def _seq(s) -> np.ndarray:
@@ -724,6 +803,28 @@ class Context:
         if st != NW_OK:
             raise NwError(st, "nw_sw_traceback")
         return out, ops[:out.n_ops].copy()
+
+    def traceback(self, d_s1, d_s2, table, scheme=(1, 0, -1), stream=None, band: int = 0, max_windows: int = 0,
+                  no_aim: bool = False):
+        """Global traceback of a device table filled with mode=MODE_NW, from (n2, n1) to
+        (0, 0) (nw_traceback): (NwAlignment, ops, NwTbStats) as align.  Ordered after the
+        fill on `stream` (default: torch's current stream), which alone is synchronised."""
+        import torch
+        n1, n2 = int(d_s1.numel()), int(d_s2.numel())
+        if stream is None:
+            stream = torch.cuda.current_stream(table.device)
+        ops = np.empty(max(n1 + n2, 1), dtype=np.uint8)
+        out, stats = NwAlignment(), NwTbStats()
+        p = params(scheme, device=self.device)
+        o = tb_opts(band, max_windows, no_aim)
+        st = lib().nw_traceback(self._h, ctypes.c_void_p(d_s1.data_ptr() if n1 else 0), n1,
+                                ctypes.c_void_p(d_s2.data_ptr() if n2 else 0), n2, ctypes.byref(p),
+                                ctypes.c_void_p(table.data_ptr()), table.shape[1], ctypes.byref(o),
+                                ctypes.c_void_p(stream.cuda_stream), ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                n1 + n2, ctypes.byref(out), ctypes.byref(stats))
+        if st != NW_OK:
+            raise NwError(st, "nw_traceback")
+        return out, ops[:out.n_ops].copy(), stats
 
     def set_trace(self, trace_tensor) -> None:
         """Debug: per-strip timeline (start, end, waits, ...: tools/trace_strips.py) into

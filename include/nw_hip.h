@@ -40,6 +40,7 @@ enum {
     NW_ERR_NODEVICE = 5,  /* no gfx950 device visible                          */
     NW_ERR_UNSUPPORTED = 6
 };
+enum { NW_ERR_TABLE = 7 };  /* traceback: a cell no move reproduces -- not a table of these params */
 
 /* nw_params.mode: global alignment (the reference fills) or Smith-Waterman local
  * alignment (BASELINE config 5; no reference counterpart -- conventions in
@@ -127,7 +128,8 @@ typedef struct nw_result {
     int32_t reserved;
 } nw_result;
 
-/* A Smith-Waterman alignment (nw_sw_align / nw_sw_traceback). */
+/* An alignment: Smith-Waterman (nw_sw_align / nw_sw_traceback) or global (nw_align /
+ * nw_traceback: begin = (0, 0), end = (n2, n1), score = t[n2][n1]). */
 typedef struct nw_alignment {
     int32_t score;           /* t[end_i][end_j], the table maximum            */
     int32_t status;
@@ -198,6 +200,43 @@ int nw_sw_align(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, cons
 /* Device-resident API ------------------------------------------------------ */
 typedef struct nw_ctx nw_ctx;
 
+/*
+ * Global alignment with on-device traceback: the path of the Needleman-Wunsch
+ * table from (n2, n1) back to (0, 0), taking at every cell the first move that
+ * reproduces t, diag > up > left (the order of serial.cpp:24-30's max); along
+ * row 0 the moves are left, along column 0 up.  ops as in nw_sw_align (path order
+ * begin -> end: 0 diagonal, 1 up, 2 left); a global path has between max(n1, n2)
+ * and n1 + n2 ops, and ops_cap >= n1 + n2 is required up front.
+ * out->begin_* = (0, 0), out->end_* = (n2, n1), out->score = t[n2][n1].
+ */
+enum { NW_TB_NO_AIM = 1 };    /* nw_tb_opts.flags */
+typedef struct nw_tb_opts {   /* NULL = defaults */
+    int32_t band;             /* window half-width B, 1..256; 0 = 256 */
+    int32_t max_windows;      /* windows (of 64 rows) per round, >= 1; 0 = 512 */
+    int32_t flags;            /* NW_TB_NO_AIM: rounds on the slope-1 diagonal instead of
+                                 aimed at (0, 0) (A/B and tests); other bits refused */
+    int32_t reserved;         /* must be 0 */
+} nw_tb_opts;
+
+typedef struct nw_tb_stats {
+    int32_t rounds, windows;  /* rounds run (one stream synchronisation each), windows launched */
+    int32_t band, max_windows; /* the geometry used */
+    int64_t tail_ops;         /* ops of the forced run along row 0 / column 0 (one memset) */
+} nw_tb_stats;
+
+/* Traceback of a device-resident table filled in NW_MODE_NW by nw_fill_device /
+ * nw_fill_device_async.  Stream-ordered after the fill on `stream` (a
+ * hipStream_t, NULL = default stream); synchronises that stream only.  `stats`
+ * may be NULL.  Refused with NW_ERR_ARG before any device work: p->mode other than
+ * NW_MODE_NW, p->flags with NW_FLAG_TIMING_ONLY or a debug bit (the table would
+ * not hold a fill), ops_cap < n1 + n2, ops == NULL with n1 + n2 > 0, band outside
+ * 0..256, max_windows < 0, unknown opts flags, reserved != 0.  NW_ERR_TABLE: the
+ * walk met a cell that no move reproduces (the table is not a fill of these
+ * sequences and parameters); reported at the end of that round. */
+int nw_traceback(nw_ctx *ctx, const int8_t *d_s1, int64_t n1, const int8_t *d_s2, int64_t n2,
+                 const nw_params *p, const int32_t *d_t, int64_t pitch, const nw_tb_opts *o,
+                 void *stream, uint8_t *ops, int64_t ops_cap, nw_alignment *out, nw_tb_stats *stats);
+
 /* Strip shape (columns per lane C, chained compute waves NC) that a fill with
  * nw_params.substrips = strip_waves = 0 uses for an n1 x n2 table: the table
  * measured by tools/tune.py (the analogue of the reference's block tuner,
@@ -265,6 +304,15 @@ int nw_fill_device(nw_ctx *ctx, const int8_t *d_s1, int64_t n1,
 int nw_sw_traceback(nw_ctx *ctx, const int8_t *d_s1, int64_t n1, const int8_t *d_s2, int64_t n2,
                     const nw_params *p, const int32_t *d_t, int64_t pitch, int64_t end_i, int64_t end_j,
                     uint8_t *ops, int64_t ops_cap, nw_alignment *out);
+
+/* One-shot global alignment from host buffers (the counterpart of nw_sw_align):
+ * copies s1 / s2 to the device, fills the table in HBM, walks it there
+ * (nw_traceback) and returns the ops.  p == NULL: the reference defaults.
+ * n1 == 0 or n2 == 0 needs no table: the ops are all ups / all lefts and the
+ * score is gap * max(n1, n2).  The refusals of nw_traceback apply, all checked
+ * before any HIP call; a host without a device answers NW_ERR_NODEVICE. */
+int nw_align(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, const nw_params *p,
+             const nw_tb_opts *o, uint8_t *ops, int64_t ops_cap, nw_alignment *out, nw_tb_stats *stats);
 
 /* Launch-only variant for timing loops: no synchronisation, no readback. */
 int nw_fill_device_async(nw_ctx *ctx, const int8_t *d_s1, int64_t n1,
@@ -494,6 +542,20 @@ void nw_free(void *p);
 
 /* Seeded synthetic sequence: i.i.d. uniform bytes in {1,2,3,4} (SplitMix64). */
 void nw_synth_bdna(uint64_t seed, int64_t n, int8_t *out);
+
+/* Alignment ops (nw_align, nw_traceback, nw_sw_align, nw_sw_traceback) on the
+ * host, no device.  The path starts at cell (begin_i, begin_j) -- (0, 0) for a
+ * global alignment, nw_alignment.begin_* for a local one -- and op k moves to the
+ * next cell: 0 pairs s1[j] with s2[i], 1 pairs s2[i] with a gap, 2 pairs s1[j]
+ * with a gap (i, j the cell before the move).  Both return NW_ERR_ARG for an op
+ * above 2 and for ops that run past either sequence.
+ * nw_ops_expand: the two gapped rows, n_ops bytes each (0 = gap, the .bdna
+ *   convention): row1 from s1, row2 from s2.
+ * nw_ops_score: the sum of match / mismatch / gap along the ops. */
+int nw_ops_expand(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t begin_i,
+                  int64_t begin_j, const uint8_t *ops, int64_t n_ops, int8_t *row1, int8_t *row2);
+int nw_ops_score(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t begin_i,
+                 int64_t begin_j, const uint8_t *ops, int64_t n_ops, const nw_params *p, int64_t *score);
 
 #ifdef __cplusplus
 }
