@@ -1,5 +1,6 @@
 // nw_internal.h -- shared between the HIP kernels (nw_fill.hip) and the C-ABI
-// layer (nw_capi.cpp).  Not part of the public ABI (include/nw_hip.h is).
+// layer (nw_launch.cpp and the other host .cpp files).  Not part of the public
+// ABI (include/nw_hip.h is).
 #pragma once
 #include <stdint.h>
 
@@ -92,7 +93,7 @@ struct FillArgs {
                            // (0: its compute wave, NW_TR_PUB_COMPUTE=1 for A/B)
     int64_t tr_y0;
     // the unfed leading strip sleeps lead_sleep x 64 clocks per 64-step iteration
-    // (horizontal (4, 1) strips: 8, nw_capi.cpp kTbandLeadSleep; NW_LEAD_SLEEP overrides)
+    // (horizontal (4, 1) strips: 8, nw_launch.cpp kTbandLeadSleep; NW_LEAD_SLEEP overrides)
     int32_t lead_sleep;
     // horizontal strips: 1 = waiting strips poll with s_sleep 1 (NW_TBAND_DENSE_POLLS)
     int32_t tr_dense;

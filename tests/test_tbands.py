@@ -223,6 +223,47 @@ def test_tband_refusals(torch_gpu):
         ctx.close()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("forced", [False, True], ids=["default", "4x1w2"])
+def test_launch_kinds_share_one_workspace(torch_gpu, forced):
+    """One context's hand-off granules, tagbase, row packs, scratch and control words
+    serve every launch kind in turn: whole-table fill, horizontal band alone (row0 = 0,
+    no feeds), a larger whole-table fill (other M and gstride over the same buffers),
+    the band again, a Smith-Waterman fill, the first fill again.  Every table cell for
+    cell against the oracle and a clean status after each launch.  `forced`: the
+    whole-table fills as (4, 1) strips on 2 workers (3 slots: the 1500-column table's 6
+    strips reuse slots and tags within the launch)."""
+    torch = torch_gpu
+    rng = np.random.default_rng(11)
+    seqs = {n: rng.integers(1, 5, n).astype(np.int8) for n in (700, 300, 1500, 900)}
+    dev = {n: torch.from_numpy(s).cuda() for n, s in seqs.items()}
+    want = {(n1, n2): oracle.fill(seqs[n1], seqs[n2]) for n1, n2 in [(700, 300), (1500, 900)]}
+    want_sw = oracle.sw_fill(seqs[700], seqs[300], (1, -1, -1))
+    kw = dict(substrips=4, strip_waves=1, waves=2) if forced else {}
+    ctx = nwhip.Context(0)
+
+    def step(kind, n1, n2):
+        tab = nwhip.Context.alloc_table(n1, n2)
+        tab.fill_(-0x5A5A5A5)  # (torch.empty may hand back an earlier table's memory)
+        if kind == "fill":
+            assert ctx.fill(dev[n1], dev[n2], tab, **kw).status == nwhip.NW_OK
+        elif kind == "sw":
+            assert ctx.fill(dev[n1], dev[n2], tab, (1, -1, -1), mode=nwhip.MODE_SW).status == nwhip.NW_OK
+        else:
+            ctx.fill_tband(dev[n1], dev[n2], tab)
+        torch.cuda.synchronize()
+        assert ctx.status() == nwhip.NW_OK, f"{kind} {n1} x {n2}: {ctx.debug_failure()}"
+        np.testing.assert_array_equal(tab[:n2 + 1, :n1 + 1].cpu().numpy(),
+                                      want_sw if kind == "sw" else want[n1, n2], err_msg=f"{kind} {n1} x {n2}")
+
+    try:
+        for kind, n1, n2 in [("fill", 700, 300), ("tband", 700, 300), ("fill", 1500, 900), ("tband", 700, 300),
+                             ("sw", 700, 300), ("fill", 700, 300)]:
+            step(kind, n1, n2)
+    finally:
+        ctx.close()
+
+
 # ------------------------------------------------------------------ the row-scan finisher
 def _tband_chain(torch, s1, s2, P, scheme, waves, flags=0, row_split=None, shape=(4, 1)):
     """P bands of the (s1, s2) table, each filled by its own nw_fill_tband_async with

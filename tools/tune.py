@@ -12,7 +12,7 @@ nw_params.substrips / strip_waves).  Two steps:
                     fills, min of --reps after a warmup, bit-exact score checked)
   here:             python tools/tune.py --write gpurun_out/tune.json
                     writes fast-needleman-wunsch_amd/csrc/nw_tuned.h (the table that
-                    nw_capi.cpp make_shape consults for auto-shaped fills) and
+                    nw_shape.cpp make_shape consults for auto-shaped fills) and
                     tools/tune_table.json (the measurements, committed)
 """
 import argparse
