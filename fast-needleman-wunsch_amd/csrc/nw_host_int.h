@@ -1,5 +1,5 @@
 // nw_host_int.h -- private to the host .cpp files of libnwhip.so (nw_capi, nw_shape,
-// nw_launch, nw_links, nw_traceback, nw_hostpath): the context, the small helpers they
+// nw_launch, nw_links, nw_traceback, nw_hostpath, nw_ckpt): the context, the small helpers they
 // share and the internal functions that cross files.  Nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -106,6 +106,15 @@ bool shape_valid(const Shape &s);
 bool valid_params(const nw_params *p);
 int tb_args(int64_t n1, int64_t n2, const nw_params *p, const nw_tb_opts *o, const uint8_t *ops, int64_t ops_cap,
             const nw_alignment *out, int32_t *band, int32_t *maxwin, int32_t *aim);
+// ---- nw_launch.cpp: what every strip-chain launch shares
+bool w_range_ok(const nw_params *p, int64_t n1, int64_t i_max);
+bool perm_allowed(const nw_params *p, int32_t off);
+int launch_workspace(nw_ctx *c, const Shape &s, uint64_t ntags, int32_t nbl, void *stream, int64_t *qlen);
+// ---- nw_hostpath.cpp: the one-shot entries' device and its kept context, held
+// (locked) from host_ctx_acquire to host_ctx_release
+int host_device_of(int device, int *dev);
+int host_ctx_acquire(int dev, nw_ctx **c);
+void host_ctx_release(int dev);
 int colband_layout(int64_t n1, int64_t n2, int32_t nb, int32_t r, const nw_params *p, int cus, int64_t *sf,
                    int64_t *sc, int64_t *start, int64_t *ncols);
 

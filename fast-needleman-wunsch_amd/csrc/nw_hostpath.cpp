@@ -233,6 +233,27 @@ int host_run(int dev, const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2
 
 }  // namespace
 
+namespace nwh {
+
+int host_device_of(int device, int *dev) { return host_device(device, dev); }
+
+int host_ctx_acquire(int dev, nw_ctx **c) {
+    HostPath &h = g_host[dev];
+    h.mu.lock();
+    int st = NW_OK;
+    if (!h.c) st = nw_ctx_create(dev, &h.c);
+    if (st != NW_OK) {
+        h.mu.unlock();
+        return st;
+    }
+    *c = h.c;
+    return NW_OK;
+}
+
+void host_ctx_release(int dev) { g_host[dev].mu.unlock(); }
+
+}  // namespace nwh
+
 extern "C" {
 
 int nw_host_warmup(int device) {

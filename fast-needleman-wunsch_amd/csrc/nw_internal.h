@@ -140,7 +140,17 @@ int run_sw_traceback(const int32_t *table, int64_t pitch, int64_t n1, const uint
 int run_nw_traceback(const int32_t *table, int64_t pitch, int64_t n1, int64_t n2, const uint8_t *s1,
                      const uint8_t *s2, int32_t match, int32_t mismatch, int32_t gap, uint8_t *ops, int64_t ops_cap,
                      void *scratch, int32_t maxwin, int32_t band, int32_t aim, int64_t *info, void *stream);
-constexpr int32_t kTbBandDefault = 256;   // band half-width of the traceback windows (profiles/r03s_tb_geometry.txt)
+// the same for one row block of a checkpointed alignment (nw_traceback_block): local
+// rows 0..rows of the table, row 0 = global row row0 > 0; the walk from (rows, n1)
+// stops on row 0 (info[1..2] = (0, column reached), no tail) or runs up column 0
+// (the tail); aimed rounds follow the line from the global cell to the global (0, 0)
+int run_nw_traceback_block(const int32_t *table, int64_t pitch, int64_t n1, int64_t rows, int64_t row0,
+                           const uint8_t *s1, const uint8_t *s2, int32_t match, int32_t mismatch, int32_t gap,
+                           uint8_t *ops, int64_t ops_cap, void *scratch, int32_t maxwin, int32_t band, int32_t aim,
+                           int64_t *info, void *stream);
+// the cumulative column shift of window k of an aimed round (nw_sw.hip tb_shift)
+int64_t tb_shift_host(int64_t k, int64_t is, int64_t js, int32_t B, int32_t aim, int64_t row0);
+constexpr int32_t kTbBandDefault = 256;  // band half-width of the traceback windows (profiles/r03s_tb_geometry.txt)
 constexpr int32_t kTbMaxWinDefault = 512;  // windows per round (64 rows each)
 
 // Launch helpers implemented in nw_fill.hip.  Return hipError_t as int.

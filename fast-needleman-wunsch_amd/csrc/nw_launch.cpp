@@ -15,6 +15,10 @@ namespace {
 
 bool fits_i8(int32_t x) { return x >= -128 && x <= 127; }
 
+}  // namespace
+
+namespace nwh {  // (shared with the checkpoint sweep's launch, nw_ckpt.cpp)
+
 // The kernels hold w = t - GAP*(i+j) in int32 next to a "minus infinity" of
 // -2^29: |w| <= (max|score| + |GAP|) * (i + j) must stay below 2^28, with i_max the
 // last GLOBAL row (a band's halo row carries the values of row band->row0).  The same
@@ -59,6 +63,10 @@ int launch_workspace(nw_ctx *c, const Shape &s, uint64_t ntags, int32_t nbl, voi
     // per-launch control words: reset, keeping a failure not yet reported (nw_link.hip nw_ctrl_reset)
     return nw::launch_ctrl_reset(c->ctrl, stream) == hipSuccess ? NW_OK : NW_ERR_HIP;
 }
+
+}  // namespace nwh
+
+namespace {
 
 // What every launch's FillArgs takes from the context, the shape and the
 // parameters (after launch_workspace: it may restart tagbase); one table

@@ -185,18 +185,27 @@ __device__ __forceinline__ uint32_t xrec(uint32_t kind, uint32_t cnt, uint32_t r
     return kind | (cnt << 2) | (r << 12) | (x << 19);
 }
 
-enum : int { kTbLocal = 0, kTbGlobal = 1 };
+// kTbBlock: one K-row block of a checkpointed global alignment (nw_traceback_block),
+// the table of rows row0 .. row0 + rows whose local row 0 (global row row0 > 0) is
+// the checkpoint row: the global rule, but local row 0 is a STOP at every column --
+// the path leaves the block there -- and column 0 is forced up while i > 0.  Its
+// rounds are aimed along the GLOBAL line, from (row0 + is, js) to (0, 0).
+enum : int { kTbLocal = 0, kTbGlobal = 1, kTbBlock = 2 };
 
 // Cumulative column shift c_k of window k in a round from (is, js), is >= 1, aimed
 // at (0, 0): the line's k * kTbR * (js - is) / is, or k * (B / 2) towards it when
 // the line moves more than B / 2 columns per window (c_0 = 0; a step c_{k+1} - c_k
-// never exceeds B / 2 either way).  aim = 0: no shift.
-__host__ __device__ __forceinline__ int64_t tb_shift(int64_t k, int64_t is, int64_t js, int32_t B, int32_t aim) {
+// never exceeds B / 2 either way).  aim = 0: no shift.  row0: the global row of the
+// table's row 0 (kTbBlock) -- the line runs from (row0 + is, js) to the global
+// (0, 0); with row0 = 0 every term below is the whole table's.
+__host__ __device__ __forceinline__ int64_t tb_shift(int64_t k, int64_t is, int64_t js, int32_t B, int32_t aim,
+                                                     int64_t row0 = 0) {
     if (!aim) return 0;
-    const int64_t num = js - is, lim = B / 2;
+    const int64_t gi = is + row0;
+    const int64_t num = js - gi, lim = B / 2;
     const int64_t mag = num < 0 ? -num : num;
-    if (kTbR * mag > lim * is) return (num < 0 ? -k : k) * lim;
-    return k * kTbR * num / is;
+    if (kTbR * mag > lim * gi) return (num < 0 ? -k : k) * lim;
+    return k * kTbR * num / gi;
 }
 
 // One window's walk from entry x (row kTbR - 1) over its move codes cd[]: calls
@@ -224,13 +233,14 @@ __global__ __launch_bounds__(kTbThreads) void nw_tb_windows(const int32_t *__res
                                                             int64_t n1, const uint8_t *__restrict__ s1,
                                                             const uint8_t *__restrict__ s2, int32_t match,
                                                             int32_t mismatch, int32_t gap, int64_t is, int64_t js,
-                                                            int32_t B, int32_t aim, uint8_t *__restrict__ codes,
+                                                            int32_t B, int32_t aim, int64_t row0,
+                                                            uint8_t *__restrict__ codes,
                                                             uint32_t *__restrict__ exits) {
     __shared__ uint8_t cd[kTbR * kTbWMax];
     const int W = 2 * B + 1;
     const int k = blockIdx.x;
     const int64_t i0 = is - (int64_t)(k + 1) * kTbR + 1;
-    const int64_t dj = js - is + i0 - B - tb_shift(k, is, js, B, aim);
+    const int64_t dj = js - is + i0 - B - tb_shift(k, is, js, B, aim, row0);
     const int ncell = kTbR * W;
     uint8_t *gcd = codes + (int64_t)k * ncell;
 #pragma unroll 4
@@ -247,6 +257,12 @@ __global__ __launch_bounds__(kTbThreads) void nw_tb_windows(const int32_t *__res
         uint8_t c;
         if (KIND == kTbLocal) {
             c = in && t > 0 ? mv : kCStop;
+        } else if (KIND == kTbBlock) {
+            // local row 0 (the checkpoint row) ends the walk wherever it is met
+            c = in ? mv
+                   : i == 0 && j >= 0 && j <= n1 ? kCStop
+                   : j == 0 && i > 0 ? kCUp
+                                     : kCBad;
         } else {
             // row 0 / column 0 are forced (the loaded values are not theirs); cells
             // outside the table are bad: a valid path never reaches them
@@ -270,8 +286,9 @@ __global__ __launch_bounds__(kTbThreads) void nw_tb_windows(const int32_t *__res
 // c_{k+1} - c_k; an entry outside [0, W) ends the round at that cell, like a move
 // out of the band.
 __global__ __launch_bounds__(1024) void nw_tb_chain(const uint32_t *__restrict__ exits, int32_t nwin, int32_t B,
-                                                    int32_t aim, int64_t is, int64_t js, int64_t ops_cap,
-                                                    int64_t *__restrict__ wentry, int64_t *__restrict__ ctl) {
+                                                    int32_t aim, int64_t is, int64_t js, int64_t row0,
+                                                    int64_t ops_cap, int64_t *__restrict__ wentry,
+                                                    int64_t *__restrict__ ctl) {
     __shared__ uint32_t ex[kChain * kTbWMax];
     __shared__ int64_t st[3];  // entry x, ops offset, done
     const int W = 2 * B + 1;
@@ -295,10 +312,10 @@ __global__ __launch_bounds__(1024) void nw_tb_chain(const uint32_t *__restrict__
                 const uint32_t rec = ex[kk * W + x];
                 const uint32_t kind = rec & 3u, cnt = (rec >> 2) & 1023u, r = (rec >> 12) & 127u, xx = rec >> 19;
                 off += cnt;
-                const int64_t ck = tb_shift(k, is, js, B, aim);
+                const int64_t ck = tb_shift(k, is, js, B, aim, row0);
                 x = (int)xx;
                 if (kind == kXCont && k + 1 < nwin) {
-                    x += (int)(tb_shift(k + 1, is, js, B, aim) - ck);
+                    x += (int)(tb_shift(k + 1, is, js, B, aim, row0) - ck);
                     if (x >= 0 && x < W) continue;
                 }
                 // the round ends in window k
@@ -349,9 +366,10 @@ size_t sw_tb_scratch_bytes(int32_t maxwin, int32_t band) {
 // Windows worth launching in an aimed round whose line outruns the B / 2 step: the
 // path drifts (line step - B / 2) columns per window off the windows' centre and
 // leaves the band after about B / drift of them; later windows would be unused.
-static int32_t tb_steep_cap(int64_t is, int64_t js, int32_t B) {
-    const int64_t num = js - is, mag = num < 0 ? -num : num, lim = B / 2;
-    const int64_t drift = (kTbR * mag - lim * is) / is;
+static int32_t tb_steep_cap(int64_t is, int64_t js, int32_t B, int64_t row0) {
+    const int64_t gi = is + row0;
+    const int64_t num = js - gi, mag = num < 0 ? -num : num, lim = B / 2;
+    const int64_t drift = (kTbR * mag - lim * gi) / gi;
     return drift <= 0 ? INT32_MAX : (int32_t)std::min<int64_t>(B / drift + 2, INT32_MAX);
 }
 
@@ -359,7 +377,7 @@ template <int KIND>
 static int run_traceback(const int32_t *table, int64_t pitch, int64_t n1, const uint8_t *s1, const uint8_t *s2,
                          int32_t match, int32_t mismatch, int32_t gap, int64_t end_i, int64_t end_j, uint8_t *ops,
                          int64_t ops_cap, void *scratch, int32_t maxwin, int32_t band, int32_t aim, int64_t *info,
-                         void *stream) {
+                         void *stream, int64_t row0 = 0) {
     hipStream_t s = (hipStream_t)stream;
     for (int q = 0; q < 10; ++q) info[q] = 0;
     if (band < 1 || band > kTbBMax || maxwin < 1) return (int)hipErrorInvalidValue;
@@ -378,11 +396,11 @@ static int run_traceback(const int32_t *table, int64_t pitch, int64_t n1, const 
             break;
         }
         int32_t nwin = (int32_t)std::min<int64_t>((ci + kTbR) / kTbR, maxwin);
-        if (aim) nwin = std::min(nwin, tb_steep_cap(ci, cj, band));
+        if (aim) nwin = std::min(nwin, tb_steep_cap(ci, cj, band, row0));
         hipLaunchKernelGGL(nw_tb_windows<KIND>, dim3((unsigned)nwin), dim3(kTbThreads), 0, s, table, pitch, n1, s1,
-                           s2, match, mismatch, gap, ci, cj, band, aim, codes, exits);
-        hipLaunchKernelGGL(nw_tb_chain, dim3(1), dim3(1024), 0, s, exits, nwin, band, aim, ci, cj, ops_cap, wentry,
-                           ctl);
+                           s2, match, mismatch, gap, ci, cj, band, aim, row0, codes, exits);
+        hipLaunchKernelGGL(nw_tb_chain, dim3(1), dim3(1024), 0, s, exits, nwin, band, aim, ci, cj, row0, ops_cap,
+                           wentry, ctl);
         hipLaunchKernelGGL(nw_tb_emit, dim3((unsigned)nwin), dim3(256), 0, s, codes, band, wentry, ctl, ops);
         if ((e = hipGetLastError()) != hipSuccess) return (int)e;
         if ((e = hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
@@ -404,7 +422,8 @@ static int run_traceback(const int32_t *table, int64_t pitch, int64_t n1, const 
         ci = h[2];  // kXCont past the round's last window, or kXOut: re-centre there
         cj = h[3];
     }
-    if (KIND == kTbGlobal && info[3] == 0 && (info[1] > 0 || info[2] > 0)) {
+    // (a block's walk that ends on its row 0 is complete: only its column 0 has a tail)
+    if ((KIND == kTbGlobal || (KIND == kTbBlock && info[1] > 0)) && info[3] == 0 && (info[1] > 0 || info[2] > 0)) {
         // on row 0 / column 0 the rest of the path is forced: info[2] lefts or info[1] ups
         const int64_t tail = info[1] > 0 ? info[1] : info[2];
         if (info[1] < 0 || info[2] < 0 || (info[1] > 0 && info[2] > 0)) {
@@ -434,6 +453,24 @@ int run_nw_traceback(const int32_t *table, int64_t pitch, int64_t n1, int64_t n2
                      void *scratch, int32_t maxwin, int32_t band, int32_t aim, int64_t *info, void *stream) {
     return run_traceback<kTbGlobal>(table, pitch, n1, s1, s2, match, mismatch, gap, n2, n1, ops, ops_cap, scratch,
                                     maxwin, band, aim, info, stream);
+}
+
+// one row block of a checkpointed alignment: `table` holds local rows 0..rows (row 0 =
+// global row row0 > 0, the checkpoint), s2 the block's side characters; the walk
+// runs from local (rows, n1) to local row 0 -- info[1..2] = (0, column reached) -- or,
+// once it meets column 0, up it (the tail, info[6])
+int run_nw_traceback_block(const int32_t *table, int64_t pitch, int64_t n1, int64_t rows, int64_t row0,
+                           const uint8_t *s1, const uint8_t *s2, int32_t match, int32_t mismatch, int32_t gap,
+                           uint8_t *ops, int64_t ops_cap, void *scratch, int32_t maxwin, int32_t band, int32_t aim,
+                           int64_t *info, void *stream) {
+    return run_traceback<kTbBlock>(table, pitch, n1, s1, s2, match, mismatch, gap, rows, n1, ops, ops_cap, scratch,
+                                   maxwin, band, aim, info, stream, row0);
+}
+
+// tb_shift on the host (tests): the window shifts of a round are a function of
+// these arguments alone
+int64_t tb_shift_host(int64_t k, int64_t is, int64_t js, int32_t B, int32_t aim, int64_t row0) {
+    return tb_shift(k, is, js, B, aim, row0);
 }
 
 }  // namespace nw

@@ -139,4 +139,63 @@ int nw_traceback(nw_ctx *c, const int8_t *d_s1, int64_t n1, const int8_t *d_s2, 
     return NW_OK;
 }
 
+// One row block of a checkpointed alignment (nw_align_ckpt): the table holds global
+// rows row0 .. row0 + rows (local row 0 = the checkpoint row, as nw_fill_band_async
+// leaves it).  With row0 = 0 the block is the top of the table and the walk is
+// nw_traceback's.
+int nw_traceback_block(nw_ctx *c, const int8_t *d_s1, int64_t n1, const int8_t *d_s2_block, int64_t rows,
+                       int64_t row0, const nw_params *p, const int32_t *d_t, int64_t pitch, const nw_tb_opts *o,
+                       void *stream, uint8_t *host_ops, int64_t ops_cap, nw_alignment *out, nw_tb_stats *stats) {
+    int32_t band = 0, maxwin = 0, aim = 0;
+    int st = tb_args(n1, rows, p, o, host_ops, ops_cap, out, &band, &maxwin, &aim);
+    if (st != NW_OK) return st;
+    if (row0 < 0 || row0 + rows >= INT32_MAX) return NW_ERR_ARG;
+    if (!c || !d_t || pitch < n1 + 1 || (n1 > 0 && !d_s1) || (rows > 0 && !d_s2_block)) return NW_ERR_ARG;
+    if (row0 == 0) {
+        st = nw_traceback(c, d_s1, n1, d_s2_block, rows, p, d_t, pitch, o, stream, host_ops, ops_cap, out, stats);
+        return st;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    NW_HIP_TRY(hipSetDevice(c->device));
+    if ((st = tb_workspace(c, (size_t)std::max<int64_t>(n1 + rows, 1), rows, band, &maxwin)) != NW_OK) return st;
+    NW_HIP_TRY(hipEventRecord(c->ev0, s));
+    int64_t info[10];
+    const int he = nw::run_nw_traceback_block(d_t, pitch, n1, rows, row0, (const uint8_t *)d_s1,
+                                              (const uint8_t *)d_s2_block, p->match, p->mismatch, p->gap, c->ops,
+                                              n1 + rows, c->tbscratch, maxwin, band, aim, info, stream);
+    if (he != hipSuccess) {
+        std::fprintf(stderr, "libnwhip: traceback failed: %s\n", hipGetErrorString((hipError_t)he));
+        return NW_ERR_HIP;
+    }
+    std::memset(out, 0, sizeof *out);
+    if (stats) {
+        stats->rounds = (int32_t)info[4];
+        stats->windows = (int32_t)info[5];
+        stats->band = band;
+        stats->max_windows = maxwin;
+        stats->tail_ops = info[6];
+    }
+    const bool ok = info[3] == 0;
+    NW_HIP_TRY(hipMemcpyAsync(&out->score, d_t + rows * pitch + n1, 4, hipMemcpyDeviceToHost, s));
+    if (ok && info[0] > 0) NW_HIP_TRY(hipMemcpyAsync(host_ops, c->ops, (size_t)info[0], hipMemcpyDeviceToHost, s));
+    float ms = 0.f;
+    if ((st = tb_elapsed(c, s, &ms)) != NW_OK) return st;
+    if (!ok) {
+        out->end_i = row0 + rows;
+        out->end_j = n1;
+        out->traceback_ms = ms;
+        out->status = NW_ERR_TABLE;
+        return NW_ERR_TABLE;
+    }
+    // info[1..2] = (0, the column where the walk reached local row 0)
+    set_alignment(out, row0 + rows, n1, info, ms, NW_OK);
+    out->begin_i = row0 + info[1];
+    std::reverse(host_ops, host_ops + info[0]);
+    return NW_OK;
+}
+
+int64_t nw_debug_tb_shift(int64_t k, int64_t is, int64_t js, int32_t band, int32_t aim, int64_t row0) {
+    return nw::tb_shift_host(k, is, js, band, aim, row0);
+}
+
 }  // extern "C"

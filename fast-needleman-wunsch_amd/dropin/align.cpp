@@ -1,9 +1,12 @@
 // align.cpp -- global alignment from the command line (nw_align of libnwhip.so):
-//   nw_align A.bdna B.bdna [OUT1 OUT2] [--scheme m,mm,g]
+//   nw_align A.bdna B.bdna [OUT1 OUT2] [--scheme m,mm,g] [--mem BYTES] [--block-rows K] [--score-only]
 //   A = s1 "across the top", B = s2 "down the side", as in driver.cpp
 //   stdout: "<align ms>\nScore: <t[n2][n1]>\n" (the reference driver's format,
 //   src/common/driver.cpp:32-35); the time covers fill, traceback and transfers.
 //   OUT1 / OUT2: the two gapped rows as .bdna files, byte 0 = gap, equal length.
+//   --mem BYTES / --block-rows K: align in linear memory (nw_align_ckpt) within BYTES
+//   of device memory / in blocks of K rows (a multiple of 64); the output is the same.
+//   --score-only: no alignment, the score from the table-free sweep (nw_score).
 // Argument and missing-file errors are nw_driver's (exit 1); a device failure is
 // reported on stderr and exits 2.
 #include <chrono>
@@ -27,6 +30,9 @@ int main(int argc, char **argv) {
     nw_params p;
     nw_params_default(&p);
     std::vector<const char *> pos;
+    nw_ckpt_opts co;
+    std::memset(&co, 0, sizeof co);
+    bool ckpt = false, score_only = false;
     for (int a = 1; a < argc; ++a) {
         if (std::strcmp(argv[a], "--scheme") == 0) {
             int m, mm, g;
@@ -38,6 +44,17 @@ int main(int argc, char **argv) {
             p.mismatch = mm;
             p.gap = g;
             ++a;
+        } else if (std::strcmp(argv[a], "--mem") == 0 || std::strcmp(argv[a], "--block-rows") == 0) {
+            long long v = 0;
+            if (a + 1 >= argc || std::sscanf(argv[a + 1], "%lld", &v) != 1 || v <= 0) {
+                std::cout << "error: " << argv[a] << " expects a positive number" << std::endl;
+                return 1;
+            }
+            (std::strcmp(argv[a], "--mem") == 0 ? co.mem_bytes : co.block_rows) = v;
+            ckpt = true;
+            ++a;
+        } else if (std::strcmp(argv[a], "--score-only") == 0) {
+            score_only = true;
         } else {
             pos.push_back(argv[a]);
         }
@@ -60,7 +77,16 @@ int main(int argc, char **argv) {
     nw_alignment al;
 
     auto wallStart = std::chrono::system_clock::now();
-    const int st = nw_align(s1, n1, s2, n2, &p, nullptr, ops.data(), n1 + n2, &al, nullptr);
+    int st;
+    if (score_only) {
+        nw_result r;
+        st = nw_score(s1, n1, s2, n2, &p, &r);
+        al.score = r.score;
+    } else if (ckpt) {
+        st = nw_align_ckpt(s1, n1, s2, n2, &p, &co, nullptr, ops.data(), n1 + n2, &al, nullptr);
+    } else {
+        st = nw_align(s1, n1, s2, n2, &p, nullptr, ops.data(), n1 + n2, &al, nullptr);
+    }
     auto wallDiff = std::chrono::system_clock::now() - wallStart;
     if (st != NW_OK) {
         std::fprintf(stderr, "nw_align (libnwhip): %s\n", nw_strerror(st));
@@ -70,7 +96,7 @@ int main(int argc, char **argv) {
     std::cout << wallMsec;
     std::cout << "\nScore: " << al.score << std::endl;
 
-    if (pos.size() == 4) {
+    if (pos.size() == 4 && !score_only) {
         std::vector<int8_t> row1((size_t)al.n_ops), row2((size_t)al.n_ops);
         if (nw_ops_expand(s1, n1, s2, n2, al.begin_i, al.begin_j, ops.data(), al.n_ops, row1.data(), row2.data()) !=
             NW_OK) {

@@ -38,7 +38,8 @@ EXPORTS = ["nw_params_default", "nw_strerror", "nw_version", "nw_fill", "nw_tabl
            "nw_fill_colband_async", "nw_link_alloc", "nw_link_wait_async", "nw_link_signal_async",
            "nw_link_status", "nw_host_warmup", "nw_host_release", "nw_halo_alloc_regions",
            "nw_fill_band_cycle_async", "nw_fill_tband_async", "nw_link_wait_ctx_async", "nw_debug_failure",
-           "nw_traceback", "nw_align", "nw_ops_expand", "nw_ops_score"]
+           "nw_traceback", "nw_align", "nw_ops_expand", "nw_ops_score", "nw_ckpt_plan", "nw_ckpt_bytes", "nw_ckpt_peak_bytes",
+           "nw_ckpt_sweep_async", "nw_score", "nw_traceback_block", "nw_align_ckpt", "nw_debug_tb_shift"]
 IPC_HANDLE_BYTES = 64
 
 
@@ -78,6 +79,20 @@ class NwTbStats(ctypes.Structure):
                 ("max_windows", ctypes.c_int32), ("tail_ops", ctypes.c_int64)]
 
 
+class NwCkptOpts(ctypes.Structure):
+    """nw_ckpt_opts (include/nw_hip.h): block height and device budget of nw_align_ckpt (0 = planned)."""
+    _fields_ = [("block_rows", ctypes.c_int64), ("mem_bytes", ctypes.c_int64), ("reserved", ctypes.c_int32 * 4)]
+
+
+class NwCkptStats(ctypes.Structure):
+    """nw_ckpt_stats (include/nw_hip.h): the plan of a checkpointed alignment and what it ran."""
+    _fields_ = [("block_rows", ctypes.c_int64), ("blocks", ctypes.c_int64), ("ckpt_bytes", ctypes.c_int64),
+                ("block_bytes", ctypes.c_int64), ("peak_bytes", ctypes.c_int64), ("refill_cells", ctypes.c_int64),
+                ("rounds", ctypes.c_int32), ("windows", ctypes.c_int32), ("sweep_ms", ctypes.c_double),
+                ("refill_ms", ctypes.c_double), ("traceback_ms", ctypes.c_double)]
+
+
+CKPT_TAG = 1   # NW_CKPT_TAG: the tag of every checkpoint granule (nw_band.tag of a re-fill)
 TB_NO_AIM = 1  # nw_tb_opts.flags NW_TB_NO_AIM: diagonal rounds instead of rounds aimed at (0, 0)
 
 
@@ -159,6 +174,26 @@ def lib() -> ctypes.CDLL:
     L.nw_align.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.POINTER(NwParams),
                            ctypes.POINTER(NwTbOpts), _u8p, ctypes.c_int64, ctypes.POINTER(NwAlignment),
                            ctypes.POINTER(NwTbStats)]
+    L.nw_ckpt_plan.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(NwCkptStats)]
+    L.nw_ckpt_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
+    L.nw_ckpt_bytes.restype = ctypes.c_int64
+    L.nw_ckpt_peak_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
+    L.nw_ckpt_peak_bytes.restype = ctypes.c_int64
+    L.nw_ckpt_sweep_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                      ctypes.c_int64, ctypes.POINTER(NwParams), ctypes.c_int64, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p]
+    L.nw_score.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.POINTER(NwParams),
+                           ctypes.POINTER(NwResult)]
+    L.nw_traceback_block.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                     ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(NwParams), ctypes.c_void_p,
+                                     ctypes.c_int64, ctypes.POINTER(NwTbOpts), ctypes.c_void_p, _u8p, ctypes.c_int64,
+                                     ctypes.POINTER(NwAlignment), ctypes.POINTER(NwTbStats)]
+    L.nw_align_ckpt.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.POINTER(NwParams),
+                                ctypes.POINTER(NwCkptOpts), ctypes.POINTER(NwTbOpts), _u8p, ctypes.c_int64,
+                                ctypes.POINTER(NwAlignment), ctypes.POINTER(NwCkptStats)]
+    L.nw_debug_tb_shift.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                    ctypes.c_int64]
+    L.nw_debug_tb_shift.restype = ctypes.c_int64
     L.nw_ops_expand.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _u8p,
                                 ctypes.c_int64, _i8p, _i8p]
     L.nw_ops_score.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _u8p,
@@ -314,6 +349,59 @@ def align(s1, s2, scheme=(1, 0, -1), band: int = 0, max_windows: int = 0, no_aim
                         ctypes.byref(out), ctypes.byref(stats))
     if st != NW_OK:
         raise NwError(st, "nw_align")
+    return out, ops[:out.n_ops].copy(), stats
+
+
+def ckpt_plan(n1: int, n2: int, mem_bytes: int) -> NwCkptStats:
+    """The block height a checkpointed alignment of an n1 x n2 pair gets within mem_bytes
+    of device memory (nw_ckpt_plan; host only): block_rows, blocks, ckpt_bytes,
+    block_bytes, peak_bytes.  Raises NwError(NW_ERR_OOM) when 64-row blocks do not fit."""
+    plan = NwCkptStats()
+    st = lib().nw_ckpt_plan(int(n1), int(n2), int(mem_bytes), ctypes.byref(plan))
+    if st != NW_OK:
+        raise NwError(st, "nw_ckpt_plan")
+    return plan
+
+
+def ckpt_peak_bytes(n1: int, n2: int, block_rows: int) -> int:
+    """Device memory of an alignment in blocks of block_rows rows (nw_ckpt_peak_bytes)."""
+    return int(lib().nw_ckpt_peak_bytes(int(n1), int(n2), int(block_rows)))
+
+
+def ckpt_bytes(n1: int, n2: int, block_rows: int) -> int:
+    return int(lib().nw_ckpt_bytes(int(n1), int(n2), int(block_rows)))
+
+
+def score_sweep(s1, s2, scheme=(1, 0, -1), waves: int = 0, device: int = -1, flags: int = 0,
+                timeout_ms: int = 0) -> NwResult:
+    """Score of the global alignment without a table (nw_score: the checkpoint sweep
+    with no checkpoints): NwResult with score, cells, kernel_ms; table_bytes = 0."""
+    a, b = _seq(s1), _seq(s2)
+    r = NwResult()
+    p = params(scheme, waves, device, flags=flags, timeout_ms=timeout_ms)
+    st = lib().nw_score(a.ctypes.data_as(_i8p), a.size, b.ctypes.data_as(_i8p), b.size, ctypes.byref(p),
+                        ctypes.byref(r))
+    if st != NW_OK:
+        raise NwError(st, "nw_score")
+    return r
+
+
+def align_ckpt(s1, s2, scheme=(1, 0, -1), block_rows: int = 0, mem_bytes: int = 0, band: int = 0,
+               max_windows: int = 0, no_aim: bool = False, device: int = -1, flags: int = 0):
+    """Global alignment in linear memory (nw_align_ckpt): (NwAlignment, ops, NwCkptStats),
+    the ops byte-identical to align's.  block_rows: K, a multiple of 64 (0: planned
+    within mem_bytes; mem_bytes = 0: 80 % of the free device memory)."""
+    a, b = _seq(s1), _seq(s2)
+    ops = np.empty(max(a.size + b.size, 1), dtype=np.uint8)
+    out, stats = NwAlignment(), NwCkptStats()
+    p = params(scheme, device=device, flags=flags)
+    o = tb_opts(band, max_windows, no_aim)
+    co = NwCkptOpts(int(block_rows), int(mem_bytes))
+    st = lib().nw_align_ckpt(a.ctypes.data_as(_i8p), a.size, b.ctypes.data_as(_i8p), b.size, ctypes.byref(p),
+                             ctypes.byref(co), ctypes.byref(o), ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                             a.size + b.size, ctypes.byref(out), ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_align_ckpt")
     return out, ops[:out.n_ops].copy(), stats
 
 
@@ -824,6 +912,60 @@ class Context:
                                 n1 + n2, ctypes.byref(out), ctypes.byref(stats))
         if st != NW_OK:
             raise NwError(st, "nw_traceback")
+        return out, ops[:out.n_ops].copy(), stats
+
+    def ckpt_sweep(self, d_s1, d_s2, K: int, scheme=(1, 0, -1), stream=None, waves: int = 0, flags: int = 0,
+                   timeout_ms: int = 0, granules: bool = False):
+        """The checkpoint sweep (nw_ckpt_sweep_async) of the table of (d_s1, d_s2), which
+        is not stored: (score, rows) with rows the table's rows K, 2K, .. as an int32
+        tensor of shape (nck, n1 + 1), nck = ceil(n2 / K) - 1.  granules=True returns the
+        raw int64 granules {CKPT_TAG | t} instead -- row r is what fill_band takes as
+        halo_in with tag=CKPT_TAG.  Synchronises `stream` and raises on a timeout."""
+        import torch
+        n1, n2 = int(d_s1.numel()), int(d_s2.numel())
+        if stream is None:
+            stream = torch.cuda.current_stream(d_s1.device)
+        nck = ckpt_bytes(n1, n2, K) // (8 * (n1 + 1))
+        with torch.cuda.stream(stream):
+            gran = torch.zeros((nck, n1 + 1), dtype=torch.int64, device=d_s1.device)
+            sc = torch.zeros(1, dtype=torch.int32, device=d_s1.device)
+        p = params(scheme, waves, self.device, flags, timeout_ms=timeout_ms)
+        st = lib().nw_ckpt_sweep_async(self._h, ctypes.c_void_p(d_s1.data_ptr() if n1 else 0), n1,
+                                       ctypes.c_void_p(d_s2.data_ptr() if n2 else 0), n2, ctypes.byref(p), int(K),
+                                       ctypes.c_void_p(gran.data_ptr() if nck else 0), ctypes.c_void_p(sc.data_ptr()),
+                                       ctypes.c_void_p(stream.cuda_stream))
+        if st != NW_OK:
+            raise NwError(st, "nw_ckpt_sweep_async")
+        st = self.status(stream)
+        if st != NW_OK:
+            raise NwError(st, "nw_ckpt_sweep_async")
+        if granules:
+            return int(sc.item()), gran
+        assert bool(((gran >> 32) == CKPT_TAG).all()), "checkpoint granule without its tag"
+        return int(sc.item()), (gran & 0xFFFFFFFF).to(torch.int32)
+
+    def traceback_block(self, d_s1, d_s2_block, table, row0: int, scheme=(1, 0, -1), stream=None, band: int = 0,
+                        max_windows: int = 0, no_aim: bool = False):
+        """Traceback of one row block (nw_traceback_block): table rows 0..len(d_s2_block)
+        hold global rows row0 .. of the table over columns 0..len(d_s1) (as fill_band
+        leaves them).  (NwAlignment, ops, NwTbStats): the walk from the block's last row
+        at column n1 to its row 0 -- begin_j is where it arrived."""
+        import torch
+        n1, rows = int(d_s1.numel()), int(d_s2_block.numel())
+        if stream is None:
+            stream = torch.cuda.current_stream(table.device)
+        ops = np.empty(max(n1 + rows, 1), dtype=np.uint8)
+        out, stats = NwAlignment(), NwTbStats()
+        p = params(scheme, device=self.device)
+        o = tb_opts(band, max_windows, no_aim)
+        st = lib().nw_traceback_block(self._h, ctypes.c_void_p(d_s1.data_ptr() if n1 else 0), n1,
+                                      ctypes.c_void_p(d_s2_block.data_ptr() if rows else 0), rows, int(row0),
+                                      ctypes.byref(p), ctypes.c_void_p(table.data_ptr()), table.shape[1],
+                                      ctypes.byref(o), ctypes.c_void_p(stream.cuda_stream),
+                                      ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), n1 + rows,
+                                      ctypes.byref(out), ctypes.byref(stats))
+        if st != NW_OK:
+            raise NwError(st, "nw_traceback_block")
         return out, ops[:out.n_ops].copy(), stats
 
     def set_trace(self, trace_tensor) -> None:

@@ -314,6 +314,95 @@ int nw_sw_traceback(nw_ctx *ctx, const int8_t *d_s1, int64_t n1, const int8_t *d
 int nw_align(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, const nw_params *p,
              const nw_tb_opts *o, uint8_t *ops, int64_t ops_cap, nw_alignment *out, nw_tb_stats *stats);
 
+/* Checkpointed (linear-memory) global alignment ------------------------------
+ * For tables that do not fit in HBM.  A forward SWEEP computes the whole table and
+ * stores only every K-th row (the checkpoints) and the score; then the K-row
+ * blocks are re-filled one at a time from the last to the first, each from its
+ * checkpoint (nw_fill_band_async into one block table), and walked with
+ * nw_traceback_block from the column where the path left the block below.
+ * Device memory: O(K * n1) for the block table + O(n1 * n2 / K) for the
+ * checkpoints; nothing proportional to n1 * n2. */
+typedef struct nw_ckpt_opts {   /* NULL = defaults */
+    int64_t block_rows;         /* K, a multiple of 64; 0 = planned (nw_ckpt_plan)           */
+    int64_t mem_bytes;          /* device budget; 0 = 80 % of the free HBM at the call       */
+    int32_t reserved[4];        /* must be 0 */
+} nw_ckpt_opts;
+
+typedef struct nw_ckpt_stats {
+    int64_t block_rows, blocks;  /* K, ceil(n2 / K)                                         */
+    int64_t ckpt_bytes;          /* checkpoint rows (nw_ckpt_bytes)                         */
+    int64_t block_bytes;         /* the block table                                         */
+    int64_t peak_bytes;          /* everything the call holds on the device at once         */
+    int64_t refill_cells;        /* cells computed by the re-fills (the sweep's n1 * n2 not counted) */
+    int32_t rounds, windows;     /* traceback rounds / windows over all blocks              */
+    double sweep_ms, refill_ms, traceback_ms;
+} nw_ckpt_stats;
+
+/* The plan for an n1 x n2 pair within mem_bytes of device memory: the largest K (a
+ * multiple of 64, at most n2 rounded up to 64) whose peak_bytes -- block table,
+ * checkpoints, hand-off workspace, sequences, row packs, ops and traceback scratch,
+ * as the allocations round them -- is <= mem_bytes; blocks = 1 when the whole table
+ * fits.  Host only (no HIP call; the hand-off workspace is sized for 256 CUs).
+ * NW_ERR_OOM when K = 64 does not fit, NW_ERR_ARG for negative sizes. */
+int nw_ckpt_plan(int64_t n1, int64_t n2, int64_t mem_bytes, nw_ckpt_stats *plan);
+
+/* peak_bytes of block height K (a multiple of 64), as nw_ckpt_plan counts it: what a
+ * caller that sets nw_ckpt_opts.block_rows itself should have free; -1 for refused
+ * arguments. */
+int64_t nw_ckpt_peak_bytes(int64_t n1, int64_t n2, int64_t K);
+
+/* Bytes of the checkpoint rows of an n1 x n2 sweep with block height K: nck = ceil(n2
+ * / K) - 1 rows (table rows K, 2K, .. nck * K) of n1 + 1 granules {tag:32 | t:32},
+ * row r at d_ckpt + r * (n1 + 1) granules -- each what nw_fill_band_async takes as
+ * halo_in with nw_band.tag = NW_CKPT_TAG. */
+#define NW_CKPT_TAG 1u
+int64_t nw_ckpt_bytes(int64_t n1, int64_t n2, int64_t K);
+
+/* The sweep on device buffers, asynchronous on `stream`: fills d_ckpt (may be NULL
+ * when K >= n2: no checkpoint rows) and *d_score = t[n2][n1]; n1, n2 >= 1.  It stores
+ * no table.  Strips of 256 columns, nw_params.waves persistent one-wave workers (0:
+ * four per CU); substrips / strip_waves are not used.  Refused before any launch
+ * with NW_ERR_ARG: invalid parameters or sizes beyond the int32 range of the w form,
+ * mode other than NW_MODE_NW, any flag but NW_FLAG_NO_PROFILE, K <= 0 or not a
+ * multiple of 64; with NW_ERR_UNSUPPORTED: kernel = NW_KERNEL_PANELS.  A wait that
+ * expires (nw_params.timeout_ms) is reported by nw_ctx_status. */
+int nw_ckpt_sweep_async(nw_ctx *ctx, const int8_t *d_s1, int64_t n1, const int8_t *d_s2, int64_t n2,
+                        const nw_params *p, int64_t K, void *d_ckpt, int32_t *d_score, void *stream);
+
+/* Score only, from host buffers: the sweep with no checkpoints.  out->score, cells,
+ * kernel_ms (the sweep), end_i / end_j, strips, waves; table_bytes = 0 -- no table is
+ * stored, so n1 x n2 is bounded by the int32 range alone.  n1 = 0 or n2 = 0 is
+ * answered without a launch.  The sweep's refusals, before any HIP call; a host
+ * without a device answers NW_ERR_NODEVICE. */
+int nw_score(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, const nw_params *p, nw_result *out);
+
+/* Traceback of one row block: d_t holds global rows row0 .. row0 + rows of the table
+ * over columns 0..n1 (local row 0 = the checkpoint row, as nw_fill_band_async writes
+ * it from halo_in), d_s2_block the block's `rows` side characters.  Walks from local
+ * (rows, n1) to local row 0: out->begin_i = row0, out->begin_j = the column where the
+ * path arrived there, out->end_* = (row0 + rows, n1), ops in begin -> end order.  A
+ * walk that meets column 0 first runs up it (one memset, stats->tail_ops) and
+ * begin_j = 0.  With row0 = 0 it is nw_traceback (row 0 walked left to (0, 0)).
+ * Aimed rounds follow the line from the global cell to the global (0, 0).
+ * Refusals and NW_ERR_TABLE as nw_traceback (ops_cap >= n1 + rows). */
+int nw_traceback_block(nw_ctx *ctx, const int8_t *d_s1, int64_t n1, const int8_t *d_s2_block, int64_t rows,
+                       int64_t row0, const nw_params *p, const int32_t *d_t, int64_t pitch, const nw_tb_opts *o,
+                       void *stream, uint8_t *ops, int64_t ops_cap, nw_alignment *out, nw_tb_stats *stats);
+
+/* One-shot global alignment in linear memory, from host buffers.  blocks = 1 (the
+ * table fits the budget): nw_align's path.  Otherwise one sweep, then per block, last
+ * to first, a re-fill of its rows over columns 0..cj and its traceback (cj: where
+ * the path left the block below; once cj = 0 the rest is one run of ups).  The ops
+ * are byte-identical to nw_align's and `out` is filled as by nw_align (fill_ms =
+ * sweep_ms + refill_ms).  NW_ERR_TABLE when the last block does not reproduce the
+ * sweep's score.  nw_align's and the sweep's refusals, and block_rows < 0 or not a
+ * multiple of 64, mem_bytes < 0, reserved != 0 (NW_ERR_ARG), before any HIP call;
+ * NW_ERR_OOM when no K fits mem_bytes; NW_ERR_NODEVICE without a device.  `stats`
+ * may be NULL. */
+int nw_align_ckpt(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, const nw_params *p,
+                  const nw_ckpt_opts *co, const nw_tb_opts *o, uint8_t *ops, int64_t ops_cap, nw_alignment *out,
+                  nw_ckpt_stats *stats);
+
 /* Launch-only variant for timing loops: no synchronisation, no readback. */
 int nw_fill_device_async(nw_ctx *ctx, const int8_t *d_s1, int64_t n1,
                          const int8_t *d_s2, int64_t n2, const nw_params *p,
@@ -531,6 +620,10 @@ int nw_debug_ctrl(nw_ctx *ctx, uint32_t *out8);
 int nw_debug_failure(nw_ctx *ctx, uint32_t *out5);
 int nw_debug_set_trace(nw_ctx *ctx, void *d_trace);
 int32_t nw_debug_trace_words(void);
+/* nw_debug_tb_shift: the cumulative column shift of window k of a traceback round
+ *   from local (is, js) with band half-width `band`, in a table whose row 0 is global
+ *   row row0 (0: a whole table; host arithmetic, no device). */
+int64_t nw_debug_tb_shift(int64_t k, int64_t is, int64_t js, int32_t band, int32_t aim, int64_t row0);
 
 /* Host helpers ------------------------------------------------------------- */
 
