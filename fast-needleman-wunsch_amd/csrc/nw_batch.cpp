@@ -1,0 +1,395 @@
+// nw_batch.cpp -- batched pairwise global alignment: the checks, the longest-first
+// order, the launches of the batch kernels (nw_batch.hip), nw_score_batch_async,
+// nw_score_batch and nw_align_batch (the directions kernel and the walk, in chunks
+// that fit the device budget).
+#include <algorithm>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+#include "nw_batch.h"
+#include "nw_host_int.h"
+
+using namespace nwh;
+
+namespace {
+
+// what every batch entry refuses in its parameters, judged without a device
+// (NW_KERNEL_PANELS, which is NW_ERR_UNSUPPORTED, comes after every NW_ERR_ARG)
+int params_check(const nw_params *p, int64_t npairs) {
+    if (!valid_params(p) || p->mode != NW_MODE_NW) return NW_ERR_ARG;
+    if ((p->flags & ~NW_FLAG_NO_PROFILE) != 0) return NW_ERR_ARG;
+    if (npairs < 0 || npairs >= INT32_MAX) return NW_ERR_ARG;
+    return NW_OK;
+}
+
+// a batch from host buffers: its sizes and the pairs that have cells, longest first
+struct Batch {
+    int64_t total1 = 0, total2 = 0, max_n2 = 0, cells = 0;
+    std::vector<int32_t> order;
+};
+
+int batch_check(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2, int64_t npairs,
+                const nw_params *p, const int32_t *scores, Batch *b) {
+    int st = params_check(p, npairs);
+    if (st != NW_OK) return st;
+    if (npairs == 0) return NW_OK;
+    if (!off1 || !off2 || !scores) return NW_ERR_ARG;
+    if (off1[0] != 0 || off2[0] != 0) return NW_ERR_ARG;
+    for (int64_t i = 0; i < npairs; ++i) {
+        const int64_t n1 = off1[i + 1] - off1[i], n2 = off2[i + 1] - off2[i];
+        if (n1 < 0 || n2 < 0 || n1 >= INT32_MAX || n2 >= INT32_MAX) return NW_ERR_ARG;
+        if (!w_range_ok(p, n1, n2)) return NW_ERR_ARG;
+        b->max_n2 = std::max(b->max_n2, n2);
+        b->cells += n1 * n2;
+    }
+    b->total1 = off1[npairs];
+    b->total2 = off2[npairs];
+    if ((b->total1 > 0 && !s1cat) || (b->total2 > 0 && !s2cat)) return NW_ERR_ARG;
+    return NW_OK;
+}
+
+void batch_order(const int64_t *off1, const int64_t *off2, int64_t npairs, Batch *b) {
+    for (int64_t i = 0; i < npairs; ++i)
+        if (off1[i + 1] > off1[i] && off2[i + 1] > off2[i]) b->order.push_back((int32_t)i);
+    auto cells = [&](int32_t i) { return (off1[i + 1] - off1[i]) * (off2[i + 1] - off2[i]); };
+    std::stable_sort(b->order.begin(), b->order.end(), [&](int32_t x, int32_t y) { return cells(x) > cells(y); });
+}
+
+// The context's workspace of a batch launch, the charmap over the concatenated s1 and
+// the row characters of the concatenated s2 (three small launches per batch, whatever
+// its number of pairs); *a gets everything but the tickets, the scores and the
+// directions, *grid the workers (nw_params.waves; 0: kCkptWavesPerCU per CU) capped at
+// `tickets`.
+int batch_prepare(nw_ctx *c, const int8_t *d_s1, const int64_t *d_off1, int64_t total1, const int8_t *d_s2,
+                  const int64_t *d_off2, int64_t total2, int64_t max_n2, const nw_params *p, int64_t tickets,
+                  void *stream, nw::BatchArgs *a, int *grid) {
+    int st;
+    int64_t waves = p->waves > 0 ? p->waves : (int64_t)c->cus * nw::kCkptWavesPerCU;
+    waves = std::max<int64_t>(1, std::min<int64_t>(waves, tickets));
+    const int64_t cstride = nw::batch_col_words(max_n2);
+    const int64_t rows_len = nw::kBatchRowPad + total2 + nw::kBatchRowTail;
+    if ((st = grow((void **)&c->rowpack, &c->rowpack_cap, (size_t)rows_len)) != NW_OK) return st;
+    if ((st = grow((void **)&c->scratch, &c->scratch_cap, (size_t)(waves * cstride) * 4)) != NW_OK) return st;
+    const bool perm_ok = perm_allowed(p, 2 * p->gap);
+    if (nw::launch_charmap((const uint8_t *)d_s1, total1, c->meta, stream) != hipSuccess) return NW_ERR_HIP;
+    if (nw::launch_batch_rows((const uint8_t *)d_s2, total2, perm_ok ? 1 : 0, c->meta, (uint8_t *)c->rowpack,
+                              stream) != hipSuccess)
+        return NW_ERR_HIP;
+    std::memset(a, 0, sizeof *a);
+    a->s1 = (const uint8_t *)d_s1;
+    a->off1 = d_off1;
+    a->rows = (const uint8_t *)c->rowpack;
+    a->off2 = d_off2;
+    a->max_n2 = (int32_t)max_n2;
+    a->ticket = c->ctrl;  // word [0], zeroed by launch_ctrl_reset
+    a->colscr = c->scratch;
+    a->cstride = cstride;
+    a->perm = perm_ok ? 1 : 0;
+    a->charmap = c->meta;
+    a->nprof = (const uint32_t *)(c->meta + 256);
+    a->match = p->match;
+    a->mismatch = p->mismatch;
+    a->gap = p->gap;
+    *grid = (int)waves;
+    return NW_OK;
+}
+
+// one launch of the batch kernel over a->npairs tickets
+int batch_run(nw_ctx *c, const nw::BatchArgs &a, bool dirs, int grid, void *stream) {
+    if (nw::launch_ctrl_reset(c->ctrl, stream) != hipSuccess) return NW_ERR_HIP;
+    if (nw::launch_batch(a, dirs, std::min(grid, std::max(a.npairs, 1)), stream) != hipSuccess) return NW_ERR_HIP;
+    c->last_waves = grid;
+    c->last_kernel = NW_KERNEL_STRIPS;
+    return NW_OK;
+}
+
+// sequences, offsets and the order of a batch on the device: one copy each
+struct BatchDev {
+    int8_t *s1 = nullptr, *s2 = nullptr;
+    int64_t *off1 = nullptr, *off2 = nullptr;
+    int32_t *order = nullptr, *scores = nullptr;
+    int64_t bytes = 0;
+    int upload(DevBufs &bufs, const int8_t *s1cat, const int64_t *h_off1, const int8_t *s2cat, const int64_t *h_off2,
+               int64_t npairs, const Batch &b) {
+        int st;
+        const size_t ob = (size_t)(npairs + 1) * 8, cnt = b.order.size();
+        if ((st = bufs.alloc((void **)&s1, (size_t)b.total1)) != NW_OK) return st;
+        if ((st = bufs.alloc((void **)&s2, (size_t)b.total2)) != NW_OK) return st;
+        if ((st = bufs.alloc((void **)&off1, ob)) != NW_OK) return st;
+        if ((st = bufs.alloc((void **)&off2, ob)) != NW_OK) return st;
+        if ((st = bufs.alloc((void **)&order, cnt * 4)) != NW_OK) return st;
+        if ((st = bufs.alloc((void **)&scores, (size_t)npairs * 4)) != NW_OK) return st;
+        if (b.total1 > 0) NW_HIP_TRY(hipMemcpy(s1, s1cat, (size_t)b.total1, hipMemcpyHostToDevice));
+        if (b.total2 > 0) NW_HIP_TRY(hipMemcpy(s2, s2cat, (size_t)b.total2, hipMemcpyHostToDevice));
+        NW_HIP_TRY(hipMemcpy(off1, h_off1, ob, hipMemcpyHostToDevice));
+        NW_HIP_TRY(hipMemcpy(off2, h_off2, ob, hipMemcpyHostToDevice));
+        NW_HIP_TRY(hipMemcpy(order, b.order.data(), cnt * 4, hipMemcpyHostToDevice));
+        return NW_OK;
+    }
+    static int64_t need(int64_t npairs, const Batch &b) {
+        return b.total1 + b.total2 + 2 * (npairs + 1) * 8 + (int64_t)b.order.size() * 4 + npairs * 4;
+    }
+};
+
+// what batch_prepare makes the context hold
+int64_t workspace_need(const Batch &b, int64_t waves) {
+    return nw::kBatchRowPad + b.total2 + nw::kBatchRowTail + waves * nw::batch_col_words(b.max_n2) * 4 +
+           nw::kMetaBytes + nw::kCtrlWords * 4;
+}
+
+int64_t workers(const nw_ctx *c, const nw_params *p, int64_t tickets) {
+    const int64_t w = p->waves > 0 ? p->waves : (int64_t)c->cus * nw::kCkptWavesPerCU;
+    return std::max<int64_t>(1, std::min<int64_t>(w, tickets));
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nw_batch_dir_bytes(int64_t n1, int64_t n2) {
+    if (n1 < 0 || n2 < 0) return -1;
+    if (n1 == 0 || n2 == 0) return 0;
+    return nw::batch_strips(n1) * nw::batch_iters(n2) * nw::kBatchDirIter;
+}
+
+int nw_score_batch_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                         const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2, int64_t max_n2,
+                         const nw_params *p, int32_t *d_scores, void *stream) {
+    int st = params_check(p, npairs);
+    if (st != NW_OK) return st;
+    if (total1 < 0 || total2 < 0 || max_n2 < 0 || max_n2 >= INT32_MAX || max_n2 > total2) return NW_ERR_ARG;
+    if (!w_range_ok(p, 0, max_n2)) return NW_ERR_ARG;
+    if (p->kernel == NW_KERNEL_PANELS) return NW_ERR_UNSUPPORTED;
+    if (!c) return NW_ERR_ARG;
+    if (npairs == 0) return NW_OK;
+    if (!d_off1 || !d_off2 || !d_scores || (total1 > 0 && !d_s1cat) || (total2 > 0 && !d_s2cat)) return NW_ERR_ARG;
+    NW_HIP_TRY(hipSetDevice(c->device));
+    nw::BatchArgs a;
+    int grid = 0;
+    if ((st = batch_prepare(c, d_s1cat, d_off1, total1, d_s2cat, d_off2, total2, max_n2, p, npairs, stream, &a,
+                            &grid)) != NW_OK)
+        return st;
+    a.npairs = (int32_t)npairs;  // (tickets in index order: the lengths are on the device)
+    a.scores = d_scores;
+    return batch_run(c, a, false, grid, stream);
+}
+
+int nw_score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                   int64_t npairs, const nw_params *p, int32_t *scores, nw_batch_stats *stats) {
+    nw_params def;
+    if (!p) {
+        nw_params_default(&def);
+        p = &def;
+    }
+    Batch b;
+    int st = batch_check(s1cat, off1, s2cat, off2, npairs, p, scores, &b);
+    if (st != NW_OK) return st;
+    if (p->kernel == NW_KERNEL_PANELS) return NW_ERR_UNSUPPORTED;
+    int dev;
+    if ((st = have_device(p, &dev)) != NW_OK) return st;
+    nw_batch_stats bs;
+    std::memset(&bs, 0, sizeof bs);
+    bs.pairs = npairs;
+    bs.cells = b.cells;
+    if (stats) *stats = bs;
+    if (npairs == 0) return NW_OK;
+    batch_order(off1, off2, npairs, &b);
+    for (int64_t i = 0; i < npairs; ++i) {  // no cells: the corner of the boundary
+        const int64_t n1 = off1[i + 1] - off1[i], n2 = off2[i + 1] - off2[i];
+        if (n1 == 0 || n2 == 0) scores[i] = (int32_t)(p->gap * std::max(n1, n2));
+    }
+    const int64_t cnt = (int64_t)b.order.size();
+    if (cnt == 0) return NW_OK;
+
+    Lease L;
+    if ((st = L.acquire(dev)) != NW_OK) return st;
+    nw_ctx *c = L.c;
+    NW_HIP_TRY(hipSetDevice(dev));
+    DevBufs bufs;
+    BatchDev d;
+    if ((st = d.upload(bufs, s1cat, off1, s2cat, off2, npairs, b)) != NW_OK) return st;
+    nw::BatchArgs a;
+    int grid = 0;
+    if ((st = batch_prepare(c, d.s1, d.off1, b.total1, d.s2, d.off2, b.total2, b.max_n2, p, cnt, nullptr, &a,
+                            &grid)) != NW_OK)
+        return st;
+    a.order = d.order;
+    a.npairs = (int32_t)cnt;
+    a.scores = d.scores;
+    NW_HIP_TRY(hipEventRecord(c->ev0, nullptr));
+    if ((st = batch_run(c, a, false, grid, nullptr)) != NW_OK) return st;
+    NW_HIP_TRY(hipEventRecord(c->ev1, nullptr));
+    std::vector<int32_t> got((size_t)npairs);
+    NW_HIP_TRY(hipMemcpy(got.data(), d.scores, (size_t)npairs * 4, hipMemcpyDeviceToHost));
+    for (int32_t i : b.order) scores[i] = got[(size_t)i];
+    float ms = 0.f;
+    NW_HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    bs.chunks = 1;
+    bs.waves = grid;
+    bs.fill_ms = ms;
+    bs.peak_bytes = BatchDev::need(npairs, b) + workspace_need(b, grid);
+    if (stats) *stats = bs;
+    return NW_OK;
+}
+
+int nw_align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                   int64_t npairs, const nw_params *p, const nw_batch_opts *o, int32_t *scores, uint8_t *ops,
+                   const int64_t *ops_off, int64_t *n_ops, nw_batch_stats *stats) {
+    nw_params def;
+    if (!p) {
+        nw_params_default(&def);
+        p = &def;
+    }
+    Batch b;
+    int st = batch_check(s1cat, off1, s2cat, off2, npairs, p, scores, &b);
+    if (st != NW_OK) return st;
+    int64_t mem = 0;
+    if (o) {
+        if (o->mem_bytes < 0) return NW_ERR_ARG;
+        for (int k = 0; k < 6; ++k)
+            if (o->reserved[k] != 0) return NW_ERR_ARG;
+        mem = o->mem_bytes;
+    }
+    if (npairs > 0) {
+        if (!ops_off || !n_ops) return NW_ERR_ARG;
+        for (int64_t i = 0; i < npairs; ++i) {
+            const int64_t need = (off1[i + 1] - off1[i]) + (off2[i + 1] - off2[i]);
+            if (ops_off[i] < 0 || ops_off[i + 1] - ops_off[i] < need) return NW_ERR_ARG;
+        }
+        if (ops_off[npairs] > 0 && !ops) return NW_ERR_ARG;
+    }
+    if (p->kernel == NW_KERNEL_PANELS) return NW_ERR_UNSUPPORTED;
+    int dev;
+    if ((st = have_device(p, &dev)) != NW_OK) return st;
+    nw_batch_stats bs;
+    std::memset(&bs, 0, sizeof bs);
+    bs.pairs = npairs;
+    bs.cells = b.cells;
+    if (stats) *stats = bs;
+    if (npairs == 0) return NW_OK;
+    batch_order(off1, off2, npairs, &b);
+    for (int64_t i = 0; i < npairs; ++i) {  // no cells: all ups or all lefts
+        const int64_t n1 = off1[i + 1] - off1[i], n2 = off2[i + 1] - off2[i];
+        if (n1 != 0 && n2 != 0) continue;
+        const int64_t n = std::max(n1, n2);
+        scores[i] = (int32_t)(p->gap * n);
+        n_ops[i] = n;
+        if (n > 0) std::memset(ops + ops_off[i], n2 > 0 ? 1 : 2, (size_t)n);
+    }
+    const int64_t cnt = (int64_t)b.order.size();
+    if (cnt == 0) return NW_OK;
+
+    Lease L;
+    if ((st = L.acquire(dev)) != NW_OK) return st;
+    nw_ctx *c = L.c;
+    NW_HIP_TRY(hipSetDevice(dev));
+    if (mem == 0) {
+        size_t free_b = 0, total_b = 0;
+        NW_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        mem = (int64_t)((double)free_b * 0.8);
+    }
+    // The chunks: consecutive runs of the longest-first order whose direction blocks
+    // and ops slots fit what the budget leaves after everything else the call holds.
+    const int64_t waves = workers(c, p, cnt);
+    const int64_t fixed = BatchDev::need(npairs, b) + workspace_need(b, waves) + cnt * 3 * 8;
+    std::vector<int64_t> dir_off((size_t)cnt), loc_off((size_t)cnt);
+    std::vector<int64_t> chunk_first;  // ticket where each chunk starts (+ the end)
+    int64_t cur_dir = 0, cur_ops = 0, max_dir = 0, max_ops = 0;
+    for (int64_t t = 0; t < cnt; ++t) {
+        const int32_t i = b.order[(size_t)t];
+        const int64_t n1 = off1[i + 1] - off1[i], n2 = off2[i + 1] - off2[i];
+        const int64_t db = nw_batch_dir_bytes(n1, n2), ob = n1 + n2;
+        bs.dir_bytes += db;
+        if (fixed + db + ob > mem) return NW_ERR_OOM;  // (this pair alone: nw_align_ckpt's case)
+        if (t == 0 || fixed + cur_dir + cur_ops + db + ob > mem) {
+            chunk_first.push_back(t);
+            cur_dir = cur_ops = 0;
+        }
+        dir_off[(size_t)t] = cur_dir;
+        loc_off[(size_t)t] = cur_ops;
+        cur_dir += db;
+        cur_ops += ob;
+        max_dir = std::max(max_dir, cur_dir);
+        max_ops = std::max(max_ops, cur_ops);
+        bs.peak_bytes = std::max(bs.peak_bytes, fixed + cur_dir + cur_ops);
+    }
+    chunk_first.push_back(cnt);
+    bs.chunks = (int64_t)chunk_first.size() - 1;
+    bs.waves = (int32_t)waves;
+
+    DevBufs bufs;
+    BatchDev d;
+    Events ef, ew;
+    if ((st = d.upload(bufs, s1cat, off1, s2cat, off2, npairs, b)) != NW_OK) return st;
+    uint8_t *d_dirs = nullptr, *d_ops = nullptr;
+    int64_t *d_dir_off = nullptr, *d_loc_off = nullptr, *d_nops = nullptr;
+    if ((st = bufs.alloc((void **)&d_dirs, (size_t)max_dir)) != NW_OK) return st;
+    if ((st = bufs.alloc((void **)&d_ops, (size_t)max_ops)) != NW_OK) return st;
+    if ((st = bufs.alloc((void **)&d_dir_off, (size_t)cnt * 8)) != NW_OK) return st;
+    if ((st = bufs.alloc((void **)&d_loc_off, (size_t)cnt * 8)) != NW_OK) return st;
+    if ((st = bufs.alloc((void **)&d_nops, (size_t)cnt * 8)) != NW_OK) return st;
+    NW_HIP_TRY(hipMemcpy(d_dir_off, dir_off.data(), (size_t)cnt * 8, hipMemcpyHostToDevice));
+    NW_HIP_TRY(hipMemcpy(d_loc_off, loc_off.data(), (size_t)cnt * 8, hipMemcpyHostToDevice));
+    NW_HIP_TRY(hipEventCreate(&ef.a));
+    NW_HIP_TRY(hipEventCreate(&ef.b));
+    NW_HIP_TRY(hipEventCreate(&ew.b));
+    nw::BatchArgs a;
+    int grid = 0;
+    if ((st = batch_prepare(c, d.s1, d.off1, b.total1, d.s2, d.off2, b.total2, b.max_n2, p, cnt, nullptr, &a,
+                            &grid)) != NW_OK)
+        return st;
+    a.scores = d.scores;
+    a.dirs = d_dirs;
+    std::vector<uint8_t> stage((size_t)max_ops);
+    for (size_t k = 0; k + 1 < chunk_first.size(); ++k) {
+        const int64_t t0 = chunk_first[k], nt = chunk_first[k + 1] - t0;
+        a.order = d.order + t0;
+        a.dir_off = d_dir_off + t0;
+        a.npairs = (int32_t)nt;
+        nw::BatchWalkArgs w;
+        w.off1 = d.off1;
+        w.off2 = d.off2;
+        w.order = a.order;
+        w.npairs = a.npairs;
+        w.dirs = d_dirs;
+        w.dir_off = a.dir_off;
+        w.ops = d_ops;
+        w.ops_off = d_loc_off + t0;
+        w.n_ops = d_nops + t0;
+        NW_HIP_TRY(hipEventRecord(ef.a, nullptr));
+        if ((st = batch_run(c, a, true, grid, nullptr)) != NW_OK) return st;
+        NW_HIP_TRY(hipEventRecord(ef.b, nullptr));
+        if (nw::launch_batch_walk(w, nullptr) != hipSuccess) return NW_ERR_HIP;
+        NW_HIP_TRY(hipEventRecord(ew.b, nullptr));
+        // the chunk's ops: one copy (which also orders the next chunk's launches after
+        // this chunk's walk), then each pair's slot into the caller's
+        const int32_t last = b.order[(size_t)(t0 + nt - 1)];
+        const int64_t chunk_ops =
+            loc_off[(size_t)(t0 + nt - 1)] + (off1[last + 1] - off1[last]) + (off2[last + 1] - off2[last]);
+        NW_HIP_TRY(hipMemcpy(stage.data(), d_ops, (size_t)chunk_ops, hipMemcpyDeviceToHost));
+        for (int64_t t = t0; t < t0 + nt; ++t) {
+            const int32_t i = b.order[(size_t)t];
+            const int64_t len = (off1[i + 1] - off1[i]) + (off2[i + 1] - off2[i]);
+            std::memcpy(ops + ops_off[i], stage.data() + loc_off[(size_t)t], (size_t)len);
+        }
+        float ms = 0.f;
+        NW_HIP_TRY(hipEventElapsedTime(&ms, ef.a, ef.b));
+        bs.fill_ms += ms;
+        NW_HIP_TRY(hipEventElapsedTime(&ms, ef.b, ew.b));
+        bs.walk_ms += ms;
+    }
+    std::vector<int32_t> got((size_t)npairs);
+    std::vector<int64_t> gotn((size_t)cnt);
+    NW_HIP_TRY(hipMemcpy(got.data(), d.scores, (size_t)npairs * 4, hipMemcpyDeviceToHost));
+    NW_HIP_TRY(hipMemcpy(gotn.data(), d_nops, (size_t)cnt * 8, hipMemcpyDeviceToHost));
+    for (int64_t t = 0; t < cnt; ++t) {
+        const int32_t i = b.order[(size_t)t];
+        scores[i] = got[(size_t)i];
+        n_ops[i] = gotn[(size_t)t];
+    }
+    if (stats) *stats = bs;
+    return NW_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,66 @@
+// nw_batch.h -- shared between the batch kernels (nw_batch.hip) and their host
+// layer (nw_batch.cpp).  Not part of the public ABI (include/nw_hip.h is).
+#pragma once
+#include <stdint.h>
+
+#include "nw_ckpt.h"  // (the sweep's strip geometry: kCkptC, kCkptCols, kCkptWavesPerCU)
+#include "nw_internal.h"
+
+namespace nw {
+
+// The batch's row characters: one copy of the concatenated s2 (raw, or mapped for the
+// v_perm tables), kBatchRowPad bytes in front of it and kBatchRowTail behind.  A lane
+// loads the 64 bytes of rows 64it - lane .. + 63 whether or not those rows exist (a
+// row outside 1..n2 is never used: the EDGE test), so the loads of the first and the
+// last pair reach at most 64 bytes before and 128 bytes past the characters.
+constexpr int kBatchRowPad = 128;
+constexpr int kBatchRowTail = 256;
+constexpr int kBatchDirIter = kWave * kWave;  // direction bytes of one 64-step iteration of a strip (16 dwords per lane)
+
+// 64-step iterations of one strip of a pair with n2 rows: the sweep's nblocks + 1
+constexpr int64_t batch_iters(int64_t n2) { return n2 / kWave + 2; }
+constexpr int64_t batch_strips(int64_t n1) { return (n1 + kCkptCols - 1) / kCkptCols; }
+// int32 words of one worker's column scratch
+constexpr int64_t batch_col_words(int64_t max_n2) { return (max_n2 + kWave - 1) / kWave * kWave + kWave; }
+
+// Everything one launch of the batch kernel needs.  Plain POD, passed by value.
+struct BatchArgs {
+    const uint8_t *s1;      // the concatenated column characters
+    const int64_t *off1;    // pair i: s1[off1[i] .. off1[i + 1])
+    const uint8_t *rows;    // the row characters (above): row y of pair i at rows[kBatchRowPad + off2[i] + y - 1]
+    const int64_t *off2;
+    const int32_t *order;   // pair of ticket t (longest first); NULL: pair t
+    int32_t npairs;         // tickets of this launch
+    int32_t max_n2;         // the column scratch holds this many rows: a longer pair is refused (score INT32_MIN)
+    uint32_t *ticket;       // zero at launch
+    int32_t *colscr;        // [grid][cstride]: a worker's right column between two strips of its pair
+    int64_t cstride;
+    int32_t perm;           // v_perm score tables allowed (the rows are then mapped)
+    const uint8_t *charmap;
+    const uint32_t *nprof;
+    int32_t match, mismatch, gap;
+    int32_t *scores;        // [pair]
+    uint8_t *dirs;          // directions kernel: ticket t's block at dirs + dir_off[t]
+    const int64_t *dir_off;
+};
+
+// The walk: one thread per ticket, from (n2, n1) to (0, 0) over the direction bits.
+struct BatchWalkArgs {
+    const int64_t *off1, *off2;
+    const int32_t *order;
+    int32_t npairs;
+    const uint8_t *dirs;
+    const int64_t *dir_off;  // [ticket]
+    uint8_t *ops;
+    const int64_t *ops_off;  // [ticket]: the pair's slot of n1 + n2 bytes
+    int64_t *n_ops;          // [ticket]
+};
+
+// mapped (perm and at most kMaxPerm distinct column characters) or raw copy of s2cat
+int launch_batch_rows(const uint8_t *d_s2, int64_t total2, int32_t perm, const uint8_t *meta, uint8_t *d_rows,
+                      void *stream);
+int launch_batch(const BatchArgs &a, bool dirs, int grid, void *stream);
+// the walk (ops end -> begin, n_ops), then the reversal into begin -> end order
+int launch_batch_walk(const BatchWalkArgs &w, void *stream);
+
+}  // namespace nw

@@ -80,48 +80,6 @@ int sweep_check(int64_t n1, int64_t n2, const nw_params *p, int64_t K) {
     return NW_OK;
 }
 
-// device buffers of one call, freed when it returns
-struct DevBufs {
-    std::vector<void *> v;
-    ~DevBufs() {
-        for (void *q : v) (void)hipFree(q);
-    }
-    int alloc(void **q, size_t bytes) {
-        *q = nullptr;
-        NW_HIP_TRY(hipMalloc(q, std::max<size_t>(bytes, 1)));
-        v.push_back(*q);
-        return NW_OK;
-    }
-};
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-};
-// the one-shot entries' context of a device, held until the call returns
-struct Lease {
-    int dev = 0;
-    bool held = false;
-    nw_ctx *c = nullptr;
-    int acquire(int d) {
-        const int st = host_ctx_acquire(d, &c);
-        dev = d;
-        held = st == NW_OK;
-        return st;
-    }
-    ~Lease() {
-        if (held) host_ctx_release(dev);
-    }
-};
-
-int have_device(const nw_params *p, int *dev) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return NW_ERR_NODEVICE;
-    return host_device_of(p->device, dev);
-}
-
 int align_blocks(int dev, const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, const nw_params *p,
                  const nw_tb_opts *o, int64_t K, uint8_t *host_ops, int64_t ops_cap, nw_alignment *out,
                  nw_ckpt_stats *cs);

@@ -135,14 +135,22 @@ int launch_tband_edges(const uint64_t *feed, int32_t *table, int64_t pitch, int6
 // reads up to index kQOff + 64 * (nblocks + 3) + 48
 int64_t rowpack_len(int32_t nblocks) { return kQOff + 64 * ((int64_t)nblocks + 4) + 16; }
 
-int launch_rowpack(const uint8_t *d_s1, int64_t n1, const uint8_t *d_s2, int64_t n2, int64_t row0,
-                   int32_t perm, uint8_t *meta, void *d_q, int64_t qlen, void *stream) {
+int launch_charmap(const uint8_t *d_s1, int64_t n1, uint8_t *meta, void *stream) {
     uint8_t *charmap = meta;
     uint32_t *nprof = (uint32_t *)(meta + 256);
     uint32_t *present = (uint32_t *)(meta + 272);
     const int64_t g = std::min<int64_t>(256, std::max<int64_t>(1, (n1 + kScanBytesPerWG - 1) / kScanBytesPerWG));
     hipLaunchKernelGGL(nw_charmap_scan, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, d_s1, n1, present);
     hipLaunchKernelGGL(nw_charmap_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, present, charmap, nprof);
+    return (int)hipGetLastError();
+}
+
+int launch_rowpack(const uint8_t *d_s1, int64_t n1, const uint8_t *d_s2, int64_t n2, int64_t row0,
+                   int32_t perm, uint8_t *meta, void *d_q, int64_t qlen, void *stream) {
+    uint8_t *charmap = meta;
+    uint32_t *nprof = (uint32_t *)(meta + 256);
+    const int ce = launch_charmap(d_s1, n1, meta, stream);
+    if (ce != (int)hipSuccess) return ce;
     const int bs = 256;
     const int64_t nb = (qlen + bs - 1) / bs;
     hipLaunchKernelGGL(nw_rowpack, dim3((unsigned)nb), dim3(bs), 0, (hipStream_t)stream, d_s2, n2,

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <vector>
 
 #include "nw_hip.h"
 #include "nw_internal.h"
@@ -117,6 +118,48 @@ int host_ctx_acquire(int dev, nw_ctx **c);
 void host_ctx_release(int dev);
 int colband_layout(int64_t n1, int64_t n2, int32_t nb, int32_t r, const nw_params *p, int cus, int64_t *sf,
                    int64_t *sc, int64_t *start, int64_t *ncols);
+
+// ---- what the one-shot entries from host buffers share (nw_ckpt.cpp, nw_batch.cpp)
+// device buffers of one call, freed when it returns
+struct DevBufs {
+    std::vector<void *> v;
+    ~DevBufs() {
+        for (void *q : v) (void)hipFree(q);
+    }
+    int alloc(void **q, size_t bytes) {
+        *q = nullptr;
+        NW_HIP_TRY(hipMalloc(q, bytes > 0 ? bytes : 1));
+        v.push_back(*q);
+        return NW_OK;
+    }
+};
+struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+// the one-shot entries' context of a device, held until the call returns
+struct Lease {
+    int dev = 0;
+    bool held = false;
+    nw_ctx *c = nullptr;
+    int acquire(int d) {
+        const int st = host_ctx_acquire(d, &c);
+        dev = d;
+        held = st == NW_OK;
+        return st;
+    }
+    ~Lease() {
+        if (held) host_ctx_release(dev);
+    }
+};
+inline int have_device(const nw_params *p, int *dev) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return NW_ERR_NODEVICE;
+    return host_device_of(p->device, dev);
+}
 
 }  // namespace nwh
 #pragma GCC visibility pop

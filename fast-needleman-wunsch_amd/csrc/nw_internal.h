@@ -154,6 +154,8 @@ constexpr int32_t kTbBandDefault = 256;  // band half-width of the traceback win
 constexpr int32_t kTbMaxWinDefault = 512;  // windows per round (64 rows each)
 
 // Launch helpers implemented in nw_fill.hip.  Return hipError_t as int.
+// charmap of s1 into meta alone (charmap[256] at meta, nprof at meta + 256)
+int launch_charmap(const uint8_t *d_s1, int64_t n1, uint8_t *meta, void *stream);
 // charmap of s1 into meta, then the row packs (mapped when perm allows it)
 int launch_rowpack(const uint8_t *d_s1, int64_t n1, const uint8_t *d_s2, int64_t n2, int64_t row0,
                    int32_t perm, uint8_t *meta, void *d_q, int64_t qlen, void *stream);

@@ -7,9 +7,16 @@
 //   --mem BYTES / --block-rows K: align in linear memory (nw_align_ckpt) within BYTES
 //   of device memory / in blocks of K rows (a multiple of 64); the output is the same.
 //   --score-only: no alignment, the score from the table-free sweep (nw_score).
+//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only]
+//   LIST: a text file, one pair "A.bdna B.bdna" per line (paths relative to the
+//   list's directory unless absolute); all pairs are aligned in ONE call
+//   (nw_align_batch; --score-only: nw_score_batch).  stdout: "<ms>\n", then one
+//   "Score: <t[n2][n1]>" line per pair, in the list's order.
 // Argument and missing-file errors are nw_driver's (exit 1); a device failure is
 // reported on stderr and exits 2.
 #include <chrono>
+#include <fstream>
+#include <sstream>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,6 +33,66 @@ static bool write_file(const char *path, const std::vector<int8_t> &row) {
     return std::fclose(f) == 0 && ok;
 }
 
+// --batch LIST: every pair of the list in one call
+static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bool score_only) {
+    std::ifstream in(list);
+    if (!in) {
+        std::cout << "ERROR: no such file " << list << std::endl;
+        return 1;
+    }
+    std::string dir(list);
+    const size_t slash = dir.find_last_of('/');
+    dir = slash == std::string::npos ? std::string() : dir.substr(0, slash + 1);
+    std::vector<int8_t> s1cat, s2cat;
+    std::vector<int64_t> off1(1, 0), off2(1, 0);
+    std::string line;
+    while (std::getline(in, line)) {
+        std::istringstream ls(line);
+        std::string fa, fb;
+        if (!(ls >> fa)) continue;  // blank line
+        if (!(ls >> fb)) {
+            std::cout << "error: --batch expects two files per line" << std::endl;
+            return 1;
+        }
+        const std::string *names[2] = {&fa, &fb};
+        for (int k = 0; k < 2; ++k) {
+            const std::string path = (*names[k])[0] == '/' ? *names[k] : dir + *names[k];
+            int8_t *s = nullptr;
+            int64_t n = 0;
+            if (nw_read_bdna(path.c_str(), &s, &n) != NW_OK) {
+                std::cout << "ERROR: no such file " << path << std::endl;
+                return 1;
+            }
+            std::vector<int8_t> &cat = k == 0 ? s1cat : s2cat;
+            cat.insert(cat.end(), s, s + n);
+            (k == 0 ? off1 : off2).push_back((int64_t)cat.size());
+            nw_free(s);
+        }
+    }
+    const int64_t npairs = (int64_t)off1.size() - 1;
+    std::vector<int32_t> scores((size_t)npairs + 1);
+    std::vector<int64_t> ops_off((size_t)npairs + 1), n_ops((size_t)npairs + 1);
+    for (int64_t i = 0; i <= npairs; ++i) ops_off[(size_t)i] = off1[(size_t)i] + off2[(size_t)i];
+    std::vector<uint8_t> ops((size_t)ops_off[(size_t)npairs] + 1);
+    nw_batch_opts bo;
+    std::memset(&bo, 0, sizeof bo);
+    bo.mem_bytes = mem_bytes;
+    auto wallStart = std::chrono::system_clock::now();
+    const int st = score_only ? nw_score_batch(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p,
+                                               scores.data(), nullptr)
+                              : nw_align_batch(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &bo,
+                                               scores.data(), ops.data(), ops_off.data(), n_ops.data(), nullptr);
+    auto wallDiff = std::chrono::system_clock::now() - wallStart;
+    if (st != NW_OK) {
+        std::fprintf(stderr, "nw_align (libnwhip): %s\n", nw_strerror(st));
+        return 2;
+    }
+    std::cout << std::chrono::duration_cast<std::chrono::milliseconds>(wallDiff).count() << "\n";
+    for (int64_t i = 0; i < npairs; ++i) std::cout << "Score: " << scores[(size_t)i] << "\n";
+    std::cout.flush();
+    return 0;
+}
+
 int main(int argc, char **argv) {
     nw_params p;
     nw_params_default(&p);
@@ -33,6 +100,7 @@ int main(int argc, char **argv) {
     nw_ckpt_opts co;
     std::memset(&co, 0, sizeof co);
     bool ckpt = false, score_only = false;
+    const char *batch = nullptr;
     for (int a = 1; a < argc; ++a) {
         if (std::strcmp(argv[a], "--scheme") == 0) {
             int m, mm, g;
@@ -55,9 +123,22 @@ int main(int argc, char **argv) {
             ++a;
         } else if (std::strcmp(argv[a], "--score-only") == 0) {
             score_only = true;
+        } else if (std::strcmp(argv[a], "--batch") == 0) {
+            if (a + 1 >= argc) {
+                std::cout << "error: --batch expects a list file" << std::endl;
+                return 1;
+            }
+            batch = argv[++a];
         } else {
             pos.push_back(argv[a]);
         }
+    }
+    if (batch != nullptr) {
+        if (!pos.empty() || co.block_rows != 0) {
+            std::cout << "error: --batch takes the list alone (and --scheme, --mem, --score-only)" << std::endl;
+            return 1;
+        }
+        return run_batch(batch, p, co.mem_bytes, score_only);
     }
     if (pos.size() != 2 && pos.size() != 4) {
         std::cout << "error: incorrect number of arguments (expected 2 or 4, got " << pos.size() << ")" << std::endl;

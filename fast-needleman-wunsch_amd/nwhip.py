@@ -39,7 +39,8 @@ EXPORTS = ["nw_params_default", "nw_strerror", "nw_version", "nw_fill", "nw_tabl
            "nw_link_status", "nw_host_warmup", "nw_host_release", "nw_halo_alloc_regions",
            "nw_fill_band_cycle_async", "nw_fill_tband_async", "nw_link_wait_ctx_async", "nw_debug_failure",
            "nw_traceback", "nw_align", "nw_ops_expand", "nw_ops_score", "nw_ckpt_plan", "nw_ckpt_bytes", "nw_ckpt_peak_bytes",
-           "nw_ckpt_sweep_async", "nw_score", "nw_traceback_block", "nw_align_ckpt", "nw_debug_tb_shift"]
+           "nw_ckpt_sweep_async", "nw_score", "nw_traceback_block", "nw_align_ckpt", "nw_debug_tb_shift",
+           "nw_batch_dir_bytes", "nw_score_batch_async", "nw_score_batch", "nw_align_batch"]
 IPC_HANDLE_BYTES = 64
 
 
@@ -90,6 +91,18 @@ class NwCkptStats(ctypes.Structure):
                 ("block_bytes", ctypes.c_int64), ("peak_bytes", ctypes.c_int64), ("refill_cells", ctypes.c_int64),
                 ("rounds", ctypes.c_int32), ("windows", ctypes.c_int32), ("sweep_ms", ctypes.c_double),
                 ("refill_ms", ctypes.c_double), ("traceback_ms", ctypes.c_double)]
+
+
+class NwBatchOpts(ctypes.Structure):
+    """nw_batch_opts (include/nw_hip.h): device budget of nw_align_batch (0 = 80 % of the free HBM)."""
+    _fields_ = [("mem_bytes", ctypes.c_int64), ("reserved", ctypes.c_int32 * 6)]
+
+
+class NwBatchStats(ctypes.Structure):
+    """nw_batch_stats (include/nw_hip.h): what a batched call ran."""
+    _fields_ = [("pairs", ctypes.c_int64), ("cells", ctypes.c_int64), ("chunks", ctypes.c_int64),
+                ("dir_bytes", ctypes.c_int64), ("peak_bytes", ctypes.c_int64), ("waves", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("fill_ms", ctypes.c_double), ("walk_ms", ctypes.c_double)]
 
 
 CKPT_TAG = 1   # NW_CKPT_TAG: the tag of every checkpoint granule (nw_band.tag of a re-fill)
@@ -191,6 +204,17 @@ def lib() -> ctypes.CDLL:
     L.nw_align_ckpt.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.POINTER(NwParams),
                                 ctypes.POINTER(NwCkptOpts), ctypes.POINTER(NwTbOpts), _u8p, ctypes.c_int64,
                                 ctypes.POINTER(NwAlignment), ctypes.POINTER(NwCkptStats)]
+    _i64p_ = ctypes.POINTER(ctypes.c_int64)
+    L.nw_batch_dir_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
+    L.nw_batch_dir_bytes.restype = ctypes.c_int64
+    L.nw_score_batch_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                       ctypes.c_int64, ctypes.POINTER(NwParams), ctypes.c_void_p, ctypes.c_void_p]
+    L.nw_score_batch.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams), _i32p,
+                                 ctypes.POINTER(NwBatchStats)]
+    L.nw_align_batch.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams),
+                                 ctypes.POINTER(NwBatchOpts), _i32p, _u8p, _i64p_, _i64p_,
+                                 ctypes.POINTER(NwBatchStats)]
     L.nw_debug_tb_shift.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                     ctypes.c_int64]
     L.nw_debug_tb_shift.restype = ctypes.c_int64
@@ -403,6 +427,69 @@ def align_ckpt(s1, s2, scheme=(1, 0, -1), block_rows: int = 0, mem_bytes: int = 
     if st != NW_OK:
         raise NwError(st, "nw_align_ckpt")
     return out, ops[:out.n_ops].copy(), stats
+
+
+def batch_dir_bytes(n1: int, n2: int) -> int:
+    """Direction bytes of one pair in align_batch, with padding (nw_batch_dir_bytes):
+    0 for an empty side, -1 for a negative size."""
+    return int(lib().nw_batch_dir_bytes(int(n1), int(n2)))
+
+
+def batch_csr(pairs):
+    """(s1cat, off1, s2cat, off2) of a list of (s1, s2) pairs: the concatenations as int8
+    arrays and the int64 offsets (npairs + 1 each) the batched calls take."""
+    a = [_seq(p[0]) for p in pairs]
+    b = [_seq(p[1]) for p in pairs]
+    off1 = np.zeros(len(pairs) + 1, np.int64)
+    off2 = np.zeros(len(pairs) + 1, np.int64)
+    off1[1:] = np.cumsum([x.size for x in a])
+    off2[1:] = np.cumsum([x.size for x in b])
+    cat1 = np.concatenate(a) if a else np.zeros(0, np.int8)
+    cat2 = np.concatenate(b) if b else np.zeros(0, np.int8)
+    return (np.ascontiguousarray(cat1, dtype=np.int8), off1, np.ascontiguousarray(cat2, dtype=np.int8), off2)
+
+
+def score_batch(pairs, scheme=(1, 0, -1), waves: int = 0, device: int = -1, flags: int = 0,
+                return_stats: bool = False):
+    """Scores of many (s1, s2) pairs in one call (nw_score_batch): an int32 array, the
+    score of pair i at index i (and the NwBatchStats with return_stats)."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    n = len(pairs)
+    scores = np.zeros(max(n, 1), np.int32)
+    stats = NwBatchStats()
+    p = params(scheme, waves, device, flags=flags)
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_score_batch(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
+                              off2.ctypes.data_as(i64p), n, ctypes.byref(p), scores.ctypes.data_as(_i32p),
+                              ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_score_batch")
+    return (scores[:n], stats) if return_stats else scores[:n]
+
+
+def align_batch(pairs, scheme=(1, 0, -1), mem_bytes: int = 0, waves: int = 0, device: int = -1, flags: int = 0):
+    """Scores and alignments of many pairs in one call (nw_align_batch): (scores, [ops of
+    pair 0, ops of pair 1, ..], NwBatchStats), each ops a uint8 array in path order (0, 0)
+    -> (n2, n1) (0 diag, 1 up, 2 left), byte-identical to align's.  mem_bytes: the device
+    budget the chunks fit (0 = 80 % of the free device memory)."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    n = len(pairs)
+    ops_off = off1 + off2
+    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
+    scores = np.zeros(max(n, 1), np.int32)
+    n_ops = np.zeros(max(n, 1), np.int64)
+    stats = NwBatchStats()
+    p = params(scheme, waves, device, flags=flags)
+    o = NwBatchOpts(int(mem_bytes))
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_align_batch(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
+                              off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(o),
+                              scores.ctypes.data_as(_i32p), ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                              ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_align_batch")
+    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
+    return scores[:n], out, stats
 
 
 def ops_expand(s1, s2, ops, begin=(0, 0)):
@@ -943,6 +1030,33 @@ class Context:
             return int(sc.item()), gran
         assert bool(((gran >> 32) == CKPT_TAG).all()), "checkpoint granule without its tag"
         return int(sc.item()), (gran & 0xFFFFFFFF).to(torch.int32)
+
+    def score_batch(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, scheme=(1, 0, -1), stream=None,
+                    waves: int = 0, flags: int = 0):
+        """Scores of a batch on device tensors (nw_score_batch_async): d_s1cat / d_s2cat
+        int8/uint8 CUDA tensors (the concatenations), d_off1 / d_off2 int64 CUDA tensors of
+        npairs + 1 offsets, max_n2 >= every pair's n2.  Returns an int32 CUDA tensor of
+        npairs scores, ordered on `stream` (default: torch's current stream); nothing is
+        synchronised.  Pairs are claimed in index order: submit them longest first."""
+        import torch
+        npairs = int(d_off1.numel()) - 1
+        assert d_off1.dtype == torch.int64 and d_off2.dtype == torch.int64 and int(d_off2.numel()) == npairs + 1
+        assert d_off1.is_contiguous() and d_off2.is_contiguous()
+        t1, t2 = int(d_s1cat.numel()), int(d_s2cat.numel())
+        if stream is None:
+            stream = torch.cuda.current_stream(d_off1.device)
+        with torch.cuda.stream(stream):
+            scores = torch.zeros(max(npairs, 1), dtype=torch.int32, device=d_off1.device)
+        p = params(scheme, waves, self.device, flags)
+        st = lib().nw_score_batch_async(self._h, ctypes.c_void_p(d_s1cat.data_ptr() if t1 else 0),
+                                        ctypes.c_void_p(d_off1.data_ptr()),
+                                        ctypes.c_void_p(d_s2cat.data_ptr() if t2 else 0),
+                                        ctypes.c_void_p(d_off2.data_ptr()), npairs, t1, t2, int(max_n2),
+                                        ctypes.byref(p), ctypes.c_void_p(scores.data_ptr()),
+                                        ctypes.c_void_p(stream.cuda_stream))
+        if st != NW_OK:
+            raise NwError(st, "nw_score_batch_async")
+        return scores[:npairs]
 
     def traceback_block(self, d_s1, d_s2_block, table, row0: int, scheme=(1, 0, -1), stream=None, band: int = 0,
                         max_windows: int = 0, no_aim: bool = False):

@@ -403,6 +403,72 @@ int nw_align_ckpt(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, co
                   const nw_ckpt_opts *co, const nw_tb_opts *o, uint8_t *ops, int64_t ops_cap, nw_alignment *out,
                   nw_ckpt_stats *stats);
 
+/* Batched pairwise global alignment ------------------------------------------
+ * Many small pairs in one call.  Pairs are given CSR-style: pair i is s1cat[off1[i] ..
+ * off1[i+1]) against s2cat[off2[i] .. off2[i+1]); the offsets are int64, non-
+ * decreasing, off[0] = 0, npairs + 1 of them.  A persistent grid of one-wave workers
+ * (nw_params.waves; 0 = four per CU, at most one per pair) claims pairs from a
+ * ticket, longest first, and each worker computes its pair's whole table alone in
+ * 256-column strips, the cells exactly the sweep's (csrc/nw_batch.hip).  Per batch:
+ * one copy of each concatenation, one alphabet decision (v_perm tables when the
+ * concatenated s1 holds at most 7 distinct characters, else byte compares) and a
+ * constant number of launches; nothing per pair.  Results land at the pair's index.
+ * Refused with NW_ERR_ARG before any HIP call: invalid parameters, mode other than
+ * NW_MODE_NW, any flag but NW_FLAG_NO_PROFILE, npairs < 0, NULL arrays with npairs >
+ * 0, offsets that do not start at 0 or decrease, a pair beyond the int32 range of
+ * the w form; then kernel = NW_KERNEL_PANELS with NW_ERR_UNSUPPORTED; then a host
+ * without a device answers NW_ERR_NODEVICE.  npairs = 0 is NW_OK.  A pair with n1 = 0
+ * or n2 = 0 has no cells: score gap * max(n1, n2), ops all ups / all lefts. */
+typedef struct nw_batch_opts {   /* NULL = defaults */
+    int64_t mem_bytes;           /* device budget of nw_align_batch; 0 = 80 % of the free HBM */
+    int32_t reserved[6];         /* must be 0 */
+} nw_batch_opts;
+
+typedef struct nw_batch_stats {
+    int64_t pairs, cells;        /* npairs, the sum of n1 * n2                              */
+    int64_t chunks;              /* launches of the batch kernel (nw_score_batch: 1)        */
+    int64_t dir_bytes;           /* direction bytes of all pairs (nw_batch_dir_bytes)       */
+    int64_t peak_bytes;          /* everything the call holds on the device at once         */
+    int32_t waves, reserved;     /* workers launched                                        */
+    double fill_ms, walk_ms;     /* device time of the batch kernel / of the walks          */
+} nw_batch_stats;
+
+/* Direction bytes of one pair in nw_align_batch: 2 bits per cell, padded to whole
+ * 64-step iterations of whole 256-column strips -- ceil(n1 / 256) * (n2 / 64 + 2) *
+ * 4096 (4096 x 4096: 1.03 x n1 * n2 / 4).  0 when a side is empty, -1 for a negative
+ * size.  Host only. */
+int64_t nw_batch_dir_bytes(int64_t n1, int64_t n2);
+
+/* Scores of a batch on device buffers, asynchronous on `stream`: d_scores[i] = t[n2_i]
+ * [n1_i].  The lengths are on the device, so the caller states total1 = off1[npairs],
+ * total2 = off2[npairs] and max_n2 >= every n2_i (the workers' column scratch is sized
+ * by it; a pair with more rows gets INT32_MIN and is not computed), pairs are claimed
+ * in index order -- submit them longest first -- and the w-form range is checked for
+ * max_n2 alone: every pair must satisfy what nw_score_batch checks.  Empty pairs are
+ * answered by the kernel.  The refusals above but for the offsets' contents; also
+ * NW_ERR_ARG: p == NULL, a negative total or max_n2, max_n2 > total2, ctx == NULL. */
+int nw_score_batch_async(nw_ctx *ctx, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                         const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2, int64_t max_n2,
+                         const nw_params *p, int32_t *d_scores, void *stream);
+
+/* Scores of a batch from host buffers: scores[i] for every pair.  p == NULL: the
+ * reference defaults; `stats` may be NULL. */
+int nw_score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                   int64_t npairs, const nw_params *p, int32_t *scores, nw_batch_stats *stats);
+
+/* Scores and alignments of a batch from host buffers.  ops_off (npairs + 1, non-
+ * decreasing) gives pair i the slot ops[ops_off[i] .. ops_off[i+1]) of at least n1_i +
+ * n2_i bytes; its n_ops[i] ops (0 diag, 1 up, 2 left) start the slot, in path order
+ * (0, 0) -> (n2, n1), byte-identical to nw_align's.  The kernel keeps 2 direction bits
+ * per cell (nw_batch_dir_bytes) and one thread per pair walks them back; the longest-
+ * first order is processed in chunks whose direction bytes and ops, with everything
+ * else the call holds, fit mem_bytes (stats: chunks, peak_bytes).  Also NW_ERR_ARG:
+ * a slot shorter than n1 + n2, NULL ops / ops_off / n_ops, mem_bytes < 0, reserved !=
+ * 0.  NW_ERR_OOM when one pair alone does not fit: that pair is nw_align_ckpt's. */
+int nw_align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                   int64_t npairs, const nw_params *p, const nw_batch_opts *o, int32_t *scores, uint8_t *ops,
+                   const int64_t *ops_off, int64_t *n_ops, nw_batch_stats *stats);
+
 /* Launch-only variant for timing loops: no synchronisation, no readback. */
 int nw_fill_device_async(nw_ctx *ctx, const int8_t *d_s1, int64_t n1,
                          const int8_t *d_s2, int64_t n2, const nw_params *p,

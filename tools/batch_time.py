@@ -1,0 +1,108 @@
+"""Times of the batched alignment against a host loop over the one-pair entries;
+writes profiles/batch_time.json.
+
+Per shape: pairs, total cells, the batched calls (nw_score_batch: fill_ms and wall;
+nw_align_batch: fill_ms, walk_ms and wall; medians of --reps runs after a warm-up),
+GCUPS, and the wall time of the same pairs through a loop of nw_score and of nw_align
+(medians of --loop-reps runs after a warm-up on the first pairs).  The loop is the
+library's one-pair path, unchanged by the batch; its scores must equal the batch's.
+
+  --shape 150 | 1000 | 8000 | mixed | all   one shape per process, so that a job can give
+                                            each its own time limit; the JSON is merged
+
+The score kernel's yardstick is the checkpoint sweep's pace on one huge table
+(profiles/ckpt_time.json: 262144^2 in 20.62 ms); `fraction_of_sweep_pace` states it.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "fast-needleman-wunsch_amd"))
+import torch  # noqa: E402
+
+import nwhip  # noqa: E402
+
+SHAPES = {"150": (16384, 150, 150), "1000": (4096, 1000, 1000), "8000": (256, 8000, 8000), "mixed": (2048, 100, 4000)}
+SWEEP_GCUPS = 262144 * 262144 / (20.62 * 1e6)  # profiles/ckpt_time.json
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--shape", default="all")
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--loop-reps", type=int, default=5)
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_time.json"))
+args = ap.parse_args()
+scheme = (1, 0, -1)
+med = statistics.median
+
+
+def wall(f):
+    t0 = time.perf_counter()
+    r = f()
+    return (time.perf_counter() - t0) * 1e3, r
+
+
+def make_pairs(name):
+    npairs, lo, hi = SHAPES[name]
+    rng = np.random.default_rng(npairs)
+    if name == "mixed":
+        lens = rng.integers(lo, hi + 1, (npairs, 2))
+    else:
+        lens = np.tile([lo, hi], (npairs, 1))
+    return [(rng.integers(1, 5, int(a)).astype(np.int8), rng.integers(1, 5, int(b)).astype(np.int8)) for a, b in lens]
+
+
+def run(name):
+    pairs = make_pairs(name)
+    cells = sum(a.size * b.size for a, b in pairs)
+    e = {"shape": name, "pairs": len(pairs), "cells": int(cells),
+         "lengths": "uniform %d..%d" % SHAPES[name][1:] if name == "mixed" else "%d x %d" % SHAPES[name][1:]}
+    # the batched calls
+    nwhip.score_batch(pairs, scheme)
+    rs = [wall(lambda: nwhip.score_batch(pairs, scheme, return_stats=True)) for _ in range(args.reps)]
+    scores = rs[0][1][0]
+    fill = med(r[1][1].fill_ms for r in rs)
+    e["score_batch"] = {"fill_ms": round(fill, 3), "wall_ms": round(med(r[0] for r in rs), 3),
+                        "gcups_kernel": round(cells / (fill * 1e6), 1), "workers": int(rs[0][1][1].waves),
+                        "fraction_of_sweep_pace": round(cells / (fill * 1e6) / SWEEP_GCUPS, 3)}
+    nwhip.align_batch(pairs, scheme)
+    ra = [wall(lambda: nwhip.align_batch(pairs, scheme)) for _ in range(args.reps)]
+    st = ra[0][1][2]
+    afill, awalk = med(r[1][2].fill_ms for r in ra), med(r[1][2].walk_ms for r in ra)
+    assert np.array_equal(ra[0][1][0], scores)
+    e["align_batch"] = {"fill_ms": round(afill, 3), "walk_ms": round(awalk, 3), "wall_ms": round(med(r[0] for r in ra), 3),
+                        "gcups_kernel": round(cells / (afill * 1e6), 1), "chunks": int(st.chunks),
+                        "dir_bytes": int(st.dir_bytes), "peak_bytes": int(st.peak_bytes)}
+    # the same pairs through the one-pair entries
+    for a, b in pairs[:32]:
+        nwhip.score_sweep(a, b, scheme)
+        nwhip.align(a, b, scheme)
+    ls = [wall(lambda: [nwhip.score_sweep(a, b, scheme).score for a, b in pairs]) for _ in range(args.loop_reps)]
+    assert np.array_equal(np.array(ls[0][1], np.int32), scores)
+    la = [wall(lambda: [nwhip.align(a, b, scheme)[0].score for a, b in pairs]) for _ in range(args.loop_reps)]
+    assert np.array_equal(np.array(la[0][1], np.int32), scores)
+    e["loop"] = {"reps": args.loop_reps, "nw_score_wall_ms": round(med(r[0] for r in ls), 1),
+                 "nw_align_wall_ms": round(med(r[0] for r in la), 1)}
+    e["score_loop_over_batch"] = round(e["loop"]["nw_score_wall_ms"] / e["score_batch"]["wall_ms"], 1)
+    e["align_loop_over_batch"] = round(e["loop"]["nw_align_wall_ms"] / e["align_batch"]["wall_ms"], 1)
+    print(json.dumps(e), flush=True)
+    return e
+
+
+rec = {"shapes": {}}
+if os.path.exists(args.out):
+    with open(args.out) as f:
+        rec = json.load(f)
+rec.update({"device": torch.cuda.get_device_name(0), "library": nwhip.version(), "scheme": list(scheme),
+            "reps": args.reps, "sweep_yardstick_gcups": round(SWEEP_GCUPS, 1)})
+for name in (list(SHAPES) if args.shape == "all" else [args.shape]):
+    rec["shapes"][name] = run(name)
+os.makedirs(os.path.dirname(args.out), exist_ok=True)
+with open(args.out, "w") as f:
+    json.dump(rec, f, indent=1)
+    f.write("\n")
