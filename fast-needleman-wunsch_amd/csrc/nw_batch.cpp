@@ -1,7 +1,10 @@
 // nw_batch.cpp -- batched pairwise global alignment: the checks, the longest-first
 // order, the launches of the batch kernels (nw_batch.hip), nw_score_batch_async,
 // nw_score_batch and nw_align_batch (the directions kernel and the walk, in chunks
-// that fit the device budget).
+// that fit the device budget).  The affine-gap entries (nw_score_batch_affine_async,
+// nw_score_batch_affine, nw_align_batch_affine; kernels in nw_batch_affine.hip) are
+// the same three bodies: a Cost tells them which kernels to launch and that a worker's
+// column scratch and a pair's direction bytes are twice the linear ones.
 #include <algorithm>
 #include <cstring>
 #include <numeric>
@@ -14,11 +17,29 @@ using namespace nwh;
 
 namespace {
 
+// the gap cost of a call: linear (L * gap) or affine (open + L * gap)
+struct Cost {
+    bool affine = false;
+    int32_t open = 0;
+    int64_t col_words(int64_t max_n2) const { return nw::batch_col_words(max_n2) * (affine ? 2 : 1); }
+    int64_t dir_bytes(int64_t n1, int64_t n2) const {
+        return affine ? nw_batch_affine_dir_bytes(n1, n2) : nw_batch_dir_bytes(n1, n2);
+    }
+    // a pair without cells: one run along the boundary
+    int32_t empty_score(const nw_params *p, int64_t n) const { return (int32_t)((n > 0 ? open : 0) + p->gap * n); }
+    bool range_ok(const nw_params *p, int64_t n1, int64_t i_max) const {
+        return affine ? affine_range_ok(p, open, n1, i_max) : w_range_ok(p, n1, i_max);
+    }
+};
+
 // what every batch entry refuses in its parameters, judged without a device
 // (NW_KERNEL_PANELS, which is NW_ERR_UNSUPPORTED, comes after every NW_ERR_ARG)
-int params_check(const nw_params *p, int64_t npairs) {
+int params_check(const nw_params *p, int64_t npairs, const Cost &cost) {
     if (!valid_params(p) || p->mode != NW_MODE_NW) return NW_ERR_ARG;
     if ((p->flags & ~NW_FLAG_NO_PROFILE) != 0) return NW_ERR_ARG;
+    // with a positive gap_open the walk would open a new gap at every step, and the ops
+    // would no longer determine the score
+    if (cost.affine && cost.open > 0) return NW_ERR_ARG;
     if (npairs < 0 || npairs >= INT32_MAX) return NW_ERR_ARG;
     return NW_OK;
 }
@@ -30,8 +51,8 @@ struct Batch {
 };
 
 int batch_check(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2, int64_t npairs,
-                const nw_params *p, const int32_t *scores, Batch *b) {
-    int st = params_check(p, npairs);
+                const nw_params *p, const Cost &cost, const int32_t *scores, Batch *b) {
+    int st = params_check(p, npairs, cost);
     if (st != NW_OK) return st;
     if (npairs == 0) return NW_OK;
     if (!off1 || !off2 || !scores) return NW_ERR_ARG;
@@ -39,7 +60,7 @@ int batch_check(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
     for (int64_t i = 0; i < npairs; ++i) {
         const int64_t n1 = off1[i + 1] - off1[i], n2 = off2[i + 1] - off2[i];
         if (n1 < 0 || n2 < 0 || n1 >= INT32_MAX || n2 >= INT32_MAX) return NW_ERR_ARG;
-        if (!w_range_ok(p, n1, n2)) return NW_ERR_ARG;
+        if (!cost.range_ok(p, n1, n2)) return NW_ERR_ARG;
         b->max_n2 = std::max(b->max_n2, n2);
         b->cells += n1 * n2;
     }
@@ -62,12 +83,12 @@ void batch_order(const int64_t *off1, const int64_t *off2, int64_t npairs, Batch
 // directions, *grid the workers (nw_params.waves; 0: kCkptWavesPerCU per CU) capped at
 // `tickets`.
 int batch_prepare(nw_ctx *c, const int8_t *d_s1, const int64_t *d_off1, int64_t total1, const int8_t *d_s2,
-                  const int64_t *d_off2, int64_t total2, int64_t max_n2, const nw_params *p, int64_t tickets,
-                  void *stream, nw::BatchArgs *a, int *grid) {
+                  const int64_t *d_off2, int64_t total2, int64_t max_n2, const nw_params *p, const Cost &cost,
+                  int64_t tickets, void *stream, nw::BatchAffineArgs *aa, int *grid) {
     int st;
     int64_t waves = p->waves > 0 ? p->waves : (int64_t)c->cus * nw::kCkptWavesPerCU;
     waves = std::max<int64_t>(1, std::min<int64_t>(waves, tickets));
-    const int64_t cstride = nw::batch_col_words(max_n2);
+    const int64_t cstride = cost.col_words(max_n2);
     const int64_t rows_len = nw::kBatchRowPad + total2 + nw::kBatchRowTail;
     if ((st = grow((void **)&c->rowpack, &c->rowpack_cap, (size_t)rows_len)) != NW_OK) return st;
     if ((st = grow((void **)&c->scratch, &c->scratch_cap, (size_t)(waves * cstride) * 4)) != NW_OK) return st;
@@ -76,7 +97,10 @@ int batch_prepare(nw_ctx *c, const int8_t *d_s1, const int64_t *d_off1, int64_t 
     if (nw::launch_batch_rows((const uint8_t *)d_s2, total2, perm_ok ? 1 : 0, c->meta, (uint8_t *)c->rowpack,
                               stream) != hipSuccess)
         return NW_ERR_HIP;
-    std::memset(a, 0, sizeof *a);
+    std::memset(aa, 0, sizeof *aa);
+    aa->gap_open = cost.open;
+    aa->eoff = nw::batch_col_words(max_n2);
+    nw::BatchArgs *a = &aa->b;
     a->s1 = (const uint8_t *)d_s1;
     a->off1 = d_off1;
     a->rows = (const uint8_t *)c->rowpack;
@@ -96,9 +120,11 @@ int batch_prepare(nw_ctx *c, const int8_t *d_s1, const int64_t *d_off1, int64_t 
 }
 
 // one launch of the batch kernel over a->npairs tickets
-int batch_run(nw_ctx *c, const nw::BatchArgs &a, bool dirs, int grid, void *stream) {
+int batch_run(nw_ctx *c, const nw::BatchAffineArgs &aa, const Cost &cost, bool dirs, int grid, void *stream) {
     if (nw::launch_ctrl_reset(c->ctrl, stream) != hipSuccess) return NW_ERR_HIP;
-    if (nw::launch_batch(a, dirs, std::min(grid, std::max(a.npairs, 1)), stream) != hipSuccess) return NW_ERR_HIP;
+    const int g = std::min(grid, std::max(aa.b.npairs, 1));
+    const int e = cost.affine ? nw::launch_batch_affine(aa, dirs, g, stream) : nw::launch_batch(aa.b, dirs, g, stream);
+    if (e != hipSuccess) return NW_ERR_HIP;
     c->last_waves = grid;
     c->last_kernel = NW_KERNEL_STRIPS;
     return NW_OK;
@@ -133,8 +159,8 @@ struct BatchDev {
 };
 
 // what batch_prepare makes the context hold
-int64_t workspace_need(const Batch &b, int64_t waves) {
-    return nw::kBatchRowPad + b.total2 + nw::kBatchRowTail + waves * nw::batch_col_words(b.max_n2) * 4 +
+int64_t workspace_need(const Batch &b, int64_t waves, const Cost &cost) {
+    return nw::kBatchRowPad + b.total2 + nw::kBatchRowTail + waves * cost.col_words(b.max_n2) * 4 +
            nw::kMetaBytes + nw::kCtrlWords * 4;
 }
 
@@ -143,47 +169,37 @@ int64_t workers(const nw_ctx *c, const nw_params *p, int64_t tickets) {
     return std::max<int64_t>(1, std::min<int64_t>(w, tickets));
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t nw_batch_dir_bytes(int64_t n1, int64_t n2) {
-    if (n1 < 0 || n2 < 0) return -1;
-    if (n1 == 0 || n2 == 0) return 0;
-    return nw::batch_strips(n1) * nw::batch_iters(n2) * nw::kBatchDirIter;
-}
-
-int nw_score_batch_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
-                         const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2, int64_t max_n2,
-                         const nw_params *p, int32_t *d_scores, void *stream) {
-    int st = params_check(p, npairs);
+int score_batch_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                      const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2, int64_t max_n2,
+                      const nw_params *p, const Cost &cost, int32_t *d_scores, void *stream) {
+    int st = params_check(p, npairs, cost);
     if (st != NW_OK) return st;
     if (total1 < 0 || total2 < 0 || max_n2 < 0 || max_n2 >= INT32_MAX || max_n2 > total2) return NW_ERR_ARG;
-    if (!w_range_ok(p, 0, max_n2)) return NW_ERR_ARG;
+    if (!cost.range_ok(p, 0, max_n2)) return NW_ERR_ARG;
     if (p->kernel == NW_KERNEL_PANELS) return NW_ERR_UNSUPPORTED;
     if (!c) return NW_ERR_ARG;
     if (npairs == 0) return NW_OK;
     if (!d_off1 || !d_off2 || !d_scores || (total1 > 0 && !d_s1cat) || (total2 > 0 && !d_s2cat)) return NW_ERR_ARG;
     NW_HIP_TRY(hipSetDevice(c->device));
-    nw::BatchArgs a;
+    nw::BatchAffineArgs aa;
     int grid = 0;
-    if ((st = batch_prepare(c, d_s1cat, d_off1, total1, d_s2cat, d_off2, total2, max_n2, p, npairs, stream, &a,
+    if ((st = batch_prepare(c, d_s1cat, d_off1, total1, d_s2cat, d_off2, total2, max_n2, p, cost, npairs, stream, &aa,
                             &grid)) != NW_OK)
         return st;
-    a.npairs = (int32_t)npairs;  // (tickets in index order: the lengths are on the device)
-    a.scores = d_scores;
-    return batch_run(c, a, false, grid, stream);
+    aa.b.npairs = (int32_t)npairs;  // (tickets in index order: the lengths are on the device)
+    aa.b.scores = d_scores;
+    return batch_run(c, aa, cost, false, grid, stream);
 }
 
-int nw_score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
-                   int64_t npairs, const nw_params *p, int32_t *scores, nw_batch_stats *stats) {
+int score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2, int64_t npairs,
+                const nw_params *p, const Cost &cost, int32_t *scores, nw_batch_stats *stats) {
     nw_params def;
     if (!p) {
         nw_params_default(&def);
         p = &def;
     }
     Batch b;
-    int st = batch_check(s1cat, off1, s2cat, off2, npairs, p, scores, &b);
+    int st = batch_check(s1cat, off1, s2cat, off2, npairs, p, cost, scores, &b);
     if (st != NW_OK) return st;
     if (p->kernel == NW_KERNEL_PANELS) return NW_ERR_UNSUPPORTED;
     int dev;
@@ -197,7 +213,7 @@ int nw_score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat
     batch_order(off1, off2, npairs, &b);
     for (int64_t i = 0; i < npairs; ++i) {  // no cells: the corner of the boundary
         const int64_t n1 = off1[i + 1] - off1[i], n2 = off2[i + 1] - off2[i];
-        if (n1 == 0 || n2 == 0) scores[i] = (int32_t)(p->gap * std::max(n1, n2));
+        if (n1 == 0 || n2 == 0) scores[i] = cost.empty_score(p, std::max(n1, n2));
     }
     const int64_t cnt = (int64_t)b.order.size();
     if (cnt == 0) return NW_OK;
@@ -209,16 +225,16 @@ int nw_score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat
     DevBufs bufs;
     BatchDev d;
     if ((st = d.upload(bufs, s1cat, off1, s2cat, off2, npairs, b)) != NW_OK) return st;
-    nw::BatchArgs a;
+    nw::BatchAffineArgs aa;
     int grid = 0;
-    if ((st = batch_prepare(c, d.s1, d.off1, b.total1, d.s2, d.off2, b.total2, b.max_n2, p, cnt, nullptr, &a,
+    if ((st = batch_prepare(c, d.s1, d.off1, b.total1, d.s2, d.off2, b.total2, b.max_n2, p, cost, cnt, nullptr, &aa,
                             &grid)) != NW_OK)
         return st;
-    a.order = d.order;
-    a.npairs = (int32_t)cnt;
-    a.scores = d.scores;
+    aa.b.order = d.order;
+    aa.b.npairs = (int32_t)cnt;
+    aa.b.scores = d.scores;
     NW_HIP_TRY(hipEventRecord(c->ev0, nullptr));
-    if ((st = batch_run(c, a, false, grid, nullptr)) != NW_OK) return st;
+    if ((st = batch_run(c, aa, cost, false, grid, nullptr)) != NW_OK) return st;
     NW_HIP_TRY(hipEventRecord(c->ev1, nullptr));
     std::vector<int32_t> got((size_t)npairs);
     NW_HIP_TRY(hipMemcpy(got.data(), d.scores, (size_t)npairs * 4, hipMemcpyDeviceToHost));
@@ -228,21 +244,21 @@ int nw_score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat
     bs.chunks = 1;
     bs.waves = grid;
     bs.fill_ms = ms;
-    bs.peak_bytes = BatchDev::need(npairs, b) + workspace_need(b, grid);
+    bs.peak_bytes = BatchDev::need(npairs, b) + workspace_need(b, grid, cost);
     if (stats) *stats = bs;
     return NW_OK;
 }
 
-int nw_align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
-                   int64_t npairs, const nw_params *p, const nw_batch_opts *o, int32_t *scores, uint8_t *ops,
-                   const int64_t *ops_off, int64_t *n_ops, nw_batch_stats *stats) {
+int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2, int64_t npairs,
+                const nw_params *p, const Cost &cost, const nw_batch_opts *o, int32_t *scores, uint8_t *ops,
+                const int64_t *ops_off, int64_t *n_ops, nw_batch_stats *stats) {
     nw_params def;
     if (!p) {
         nw_params_default(&def);
         p = &def;
     }
     Batch b;
-    int st = batch_check(s1cat, off1, s2cat, off2, npairs, p, scores, &b);
+    int st = batch_check(s1cat, off1, s2cat, off2, npairs, p, cost, scores, &b);
     if (st != NW_OK) return st;
     int64_t mem = 0;
     if (o) {
@@ -273,7 +289,7 @@ int nw_align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat
         const int64_t n1 = off1[i + 1] - off1[i], n2 = off2[i + 1] - off2[i];
         if (n1 != 0 && n2 != 0) continue;
         const int64_t n = std::max(n1, n2);
-        scores[i] = (int32_t)(p->gap * n);
+        scores[i] = cost.empty_score(p, n);
         n_ops[i] = n;
         if (n > 0) std::memset(ops + ops_off[i], n2 > 0 ? 1 : 2, (size_t)n);
     }
@@ -292,14 +308,14 @@ int nw_align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat
     // The chunks: consecutive runs of the longest-first order whose direction blocks
     // and ops slots fit what the budget leaves after everything else the call holds.
     const int64_t waves = workers(c, p, cnt);
-    const int64_t fixed = BatchDev::need(npairs, b) + workspace_need(b, waves) + cnt * 3 * 8;
+    const int64_t fixed = BatchDev::need(npairs, b) + workspace_need(b, waves, cost) + cnt * 3 * 8;
     std::vector<int64_t> dir_off((size_t)cnt), loc_off((size_t)cnt);
     std::vector<int64_t> chunk_first;  // ticket where each chunk starts (+ the end)
     int64_t cur_dir = 0, cur_ops = 0, max_dir = 0, max_ops = 0;
     for (int64_t t = 0; t < cnt; ++t) {
         const int32_t i = b.order[(size_t)t];
         const int64_t n1 = off1[i + 1] - off1[i], n2 = off2[i + 1] - off2[i];
-        const int64_t db = nw_batch_dir_bytes(n1, n2), ob = n1 + n2;
+        const int64_t db = cost.dir_bytes(n1, n2), ob = n1 + n2;
         bs.dir_bytes += db;
         if (fixed + db + ob > mem) return NW_ERR_OOM;  // (this pair alone: nw_align_ckpt's case)
         if (t == 0 || fixed + cur_dir + cur_ops + db + ob > mem) {
@@ -334,9 +350,10 @@ int nw_align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat
     NW_HIP_TRY(hipEventCreate(&ef.a));
     NW_HIP_TRY(hipEventCreate(&ef.b));
     NW_HIP_TRY(hipEventCreate(&ew.b));
-    nw::BatchArgs a;
+    nw::BatchAffineArgs aa;
+    nw::BatchArgs &a = aa.b;
     int grid = 0;
-    if ((st = batch_prepare(c, d.s1, d.off1, b.total1, d.s2, d.off2, b.total2, b.max_n2, p, cnt, nullptr, &a,
+    if ((st = batch_prepare(c, d.s1, d.off1, b.total1, d.s2, d.off2, b.total2, b.max_n2, p, cost, cnt, nullptr, &aa,
                             &grid)) != NW_OK)
         return st;
     a.scores = d.scores;
@@ -358,9 +375,10 @@ int nw_align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat
         w.ops_off = d_loc_off + t0;
         w.n_ops = d_nops + t0;
         NW_HIP_TRY(hipEventRecord(ef.a, nullptr));
-        if ((st = batch_run(c, a, true, grid, nullptr)) != NW_OK) return st;
+        if ((st = batch_run(c, aa, cost, true, grid, nullptr)) != NW_OK) return st;
         NW_HIP_TRY(hipEventRecord(ef.b, nullptr));
-        if (nw::launch_batch_walk(w, nullptr) != hipSuccess) return NW_ERR_HIP;
+        if ((cost.affine ? nw::launch_batch_affine_walk(w, nullptr) : nw::launch_batch_walk(w, nullptr)) != hipSuccess)
+            return NW_ERR_HIP;
         NW_HIP_TRY(hipEventRecord(ew.b, nullptr));
         // the chunk's ops: one copy (which also orders the next chunk's launches after
         // this chunk's walk), then each pair's slot into the caller's
@@ -390,6 +408,61 @@ int nw_align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat
     }
     if (stats) *stats = bs;
     return NW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nw_batch_dir_bytes(int64_t n1, int64_t n2) {
+    if (n1 < 0 || n2 < 0) return -1;
+    if (n1 == 0 || n2 == 0) return 0;
+    return nw::batch_strips(n1) * nw::batch_iters(n2) * nw::kBatchDirIter;
+}
+
+int64_t nw_batch_affine_dir_bytes(int64_t n1, int64_t n2) {
+    const int64_t b = nw_batch_dir_bytes(n1, n2);
+    return b < 0 ? b : 2 * b;
+}
+
+int nw_score_batch_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                         const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2, int64_t max_n2,
+                         const nw_params *p, int32_t *d_scores, void *stream) {
+    return score_batch_async(c, d_s1cat, d_off1, d_s2cat, d_off2, npairs, total1, total2, max_n2, p, Cost{}, d_scores,
+                             stream);
+}
+
+int nw_score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                   int64_t npairs, const nw_params *p, int32_t *scores, nw_batch_stats *stats) {
+    return score_batch(s1cat, off1, s2cat, off2, npairs, p, Cost{}, scores, stats);
+}
+
+int nw_align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                   int64_t npairs, const nw_params *p, const nw_batch_opts *o, int32_t *scores, uint8_t *ops,
+                   const int64_t *ops_off, int64_t *n_ops, nw_batch_stats *stats) {
+    return align_batch(s1cat, off1, s2cat, off2, npairs, p, Cost{}, o, scores, ops, ops_off, n_ops, stats);
+}
+
+int nw_score_batch_affine_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                                const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2,
+                                int64_t max_n2, const nw_params *p, int32_t gap_open, int32_t *d_scores,
+                                void *stream) {
+    return score_batch_async(c, d_s1cat, d_off1, d_s2cat, d_off2, npairs, total1, total2, max_n2, p,
+                             Cost{true, gap_open}, d_scores, stream);
+}
+
+int nw_score_batch_affine(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                          int64_t npairs, const nw_params *p, int32_t gap_open, int32_t *scores,
+                          nw_batch_stats *stats) {
+    return score_batch(s1cat, off1, s2cat, off2, npairs, p, Cost{true, gap_open}, scores, stats);
+}
+
+int nw_align_batch_affine(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                          int64_t npairs, const nw_params *p, int32_t gap_open, const nw_batch_opts *o,
+                          int32_t *scores, uint8_t *ops, const int64_t *ops_off, int64_t *n_ops,
+                          nw_batch_stats *stats) {
+    return align_batch(s1cat, off1, s2cat, off2, npairs, p, Cost{true, gap_open}, o, scores, ops, ops_off, n_ops,
+                       stats);
 }
 
 }  // extern "C"

@@ -56,11 +56,24 @@ struct BatchWalkArgs {
     int64_t *n_ops;          // [ticket]
 };
 
+// The affine-gap kernels (nw_batch_affine.hip): the linear launch's arguments, with
+// b.gap the cost of extending a gap, b.cstride twice batch_col_words (a worker keeps
+// H' and E' of a right column: E' eoff words behind H') and, in the directions kernel,
+// 4 bits per cell (twice kBatchDirIter per iteration of a strip).
+struct BatchAffineArgs {
+    BatchArgs b;
+    int32_t gap_open;  // <= 0: what a run of ups or of lefts costs once, whatever its length
+    int64_t eoff;
+};
+
 // mapped (perm and at most kMaxPerm distinct column characters) or raw copy of s2cat
 int launch_batch_rows(const uint8_t *d_s2, int64_t total2, int32_t perm, const uint8_t *meta, uint8_t *d_rows,
                       void *stream);
 int launch_batch(const BatchArgs &a, bool dirs, int grid, void *stream);
 // the walk (ops end -> begin, n_ops), then the reversal into begin -> end order
 int launch_batch_walk(const BatchWalkArgs &w, void *stream);
+// the same two for affine gaps: the walk is a machine of three states over 4 bits per cell
+int launch_batch_affine(const BatchAffineArgs &a, bool dirs, int grid, void *stream);
+int launch_batch_affine_walk(const BatchWalkArgs &w, void *stream);
 
 }  // namespace nw

@@ -31,6 +31,18 @@ bool w_range_ok(const nw_params *p, int64_t n1, int64_t i_max) {
     return (m + std::llabs(p->gap)) * (long long)(n1 + i_max + 2) < (1LL << 28);
 }
 
+// The affine-gap batch kernels hold H', E' and F' (each minus ge*(i+j)) next to the
+// same -2^29.  With m = max|score| (ge included) and go = gap_open <= 0:  H <= m*(i+j)
+// and H >= 2 go - |ge|*(i+j) (one run up, one run left), so |H'| <= 2|go| + (m +
+// |ge|)*(i+j);  E and F lie between H_neighbour + go + ge and H, one more |go|; the
+// intermediates H' + go and H'_diag + s - 2ge stay within that.  The -2^29 is never
+// added to.  So 3|go| + (m + |ge|)*(n1 + i_max + 2) < 2^28 keeps every real value
+// above -2^28, where it beats the -2^29 in every maximum, and far from overflow.
+bool affine_range_ok(const nw_params *p, int32_t gap_open, int64_t n1, int64_t i_max) {
+    const long long m = std::max({std::llabs(p->match), std::llabs(p->mismatch), std::llabs(p->gap)});
+    return 3 * std::llabs((long long)gap_open) + (m + std::llabs(p->gap)) * (long long)(n1 + i_max + 2) < (1LL << 28);
+}
+
 // v_perm score tables when every substitution score minus `off` fits int8 (the
 // kernel falls back to compares on the device when s1 holds more than kMaxPerm
 // distinct characters).  off: the table bytes are s - 2 GAP in the w form (NW, and

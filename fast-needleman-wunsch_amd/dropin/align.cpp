@@ -7,11 +7,13 @@
 //   --mem BYTES / --block-rows K: align in linear memory (nw_align_ckpt) within BYTES
 //   of device memory / in blocks of K rows (a multiple of 64); the output is the same.
 //   --score-only: no alignment, the score from the table-free sweep (nw_score).
-//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only]
+//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only] [--gap-open G]
 //   LIST: a text file, one pair "A.bdna B.bdna" per line (paths relative to the
 //   list's directory unless absolute); all pairs are aligned in ONE call
 //   (nw_align_batch; --score-only: nw_score_batch).  stdout: "<ms>\n", then one
 //   "Score: <t[n2][n1]>" line per pair, in the list's order.
+//   --gap-open G (G <= 0, with --batch only): affine gap cost, a gap of length L costs
+//   G + L * g (nw_align_batch_affine / nw_score_batch_affine).
 // Argument and missing-file errors are nw_driver's (exit 1); a device failure is
 // reported on stderr and exits 2.
 #include <chrono>
@@ -34,7 +36,7 @@ static bool write_file(const char *path, const std::vector<int8_t> &row) {
 }
 
 // --batch LIST: every pair of the list in one call
-static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bool score_only) {
+static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bool score_only, const int32_t *gap_open) {
     std::ifstream in(list);
     if (!in) {
         std::cout << "ERROR: no such file " << list << std::endl;
@@ -78,10 +80,18 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
     std::memset(&bo, 0, sizeof bo);
     bo.mem_bytes = mem_bytes;
     auto wallStart = std::chrono::system_clock::now();
-    const int st = score_only ? nw_score_batch(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p,
-                                               scores.data(), nullptr)
-                              : nw_align_batch(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &bo,
-                                               scores.data(), ops.data(), ops_off.data(), n_ops.data(), nullptr);
+    int st;
+    if (gap_open != nullptr)
+        st = score_only ? nw_score_batch_affine(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p,
+                                                *gap_open, scores.data(), nullptr)
+                        : nw_align_batch_affine(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p,
+                                                *gap_open, &bo, scores.data(), ops.data(), ops_off.data(),
+                                                n_ops.data(), nullptr);
+    else
+        st = score_only ? nw_score_batch(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p,
+                                         scores.data(), nullptr)
+                        : nw_align_batch(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &bo,
+                                         scores.data(), ops.data(), ops_off.data(), n_ops.data(), nullptr);
     auto wallDiff = std::chrono::system_clock::now() - wallStart;
     if (st != NW_OK) {
         std::fprintf(stderr, "nw_align (libnwhip): %s\n", nw_strerror(st));
@@ -101,6 +111,8 @@ int main(int argc, char **argv) {
     std::memset(&co, 0, sizeof co);
     bool ckpt = false, score_only = false;
     const char *batch = nullptr;
+    int32_t gap_open = 0;
+    bool affine = false;
     for (int a = 1; a < argc; ++a) {
         if (std::strcmp(argv[a], "--scheme") == 0) {
             int m, mm, g;
@@ -121,6 +133,15 @@ int main(int argc, char **argv) {
             (std::strcmp(argv[a], "--mem") == 0 ? co.mem_bytes : co.block_rows) = v;
             ckpt = true;
             ++a;
+        } else if (std::strcmp(argv[a], "--gap-open") == 0) {
+            int g = 0;
+            if (a + 1 >= argc || std::sscanf(argv[a + 1], "%d", &g) != 1 || g > 0) {
+                std::cout << "error: --gap-open expects a number <= 0" << std::endl;
+                return 1;
+            }
+            gap_open = g;
+            affine = true;
+            ++a;
         } else if (std::strcmp(argv[a], "--score-only") == 0) {
             score_only = true;
         } else if (std::strcmp(argv[a], "--batch") == 0) {
@@ -135,10 +156,16 @@ int main(int argc, char **argv) {
     }
     if (batch != nullptr) {
         if (!pos.empty() || co.block_rows != 0) {
-            std::cout << "error: --batch takes the list alone (and --scheme, --mem, --score-only)" << std::endl;
+            std::cout << "error: --batch takes the list alone (and --scheme, --mem, --score-only, --gap-open)"
+                      << std::endl;
             return 1;
         }
-        return run_batch(batch, p, co.mem_bytes, score_only);
+        return run_batch(batch, p, co.mem_bytes, score_only, affine ? &gap_open : nullptr);
+    }
+    if (affine) {
+        std::cout << "error: --gap-open needs --batch (affine gaps are built for the batched alignment only)"
+                  << std::endl;
+        return 1;
     }
     if (pos.size() != 2 && pos.size() != 4) {
         std::cout << "error: incorrect number of arguments (expected 2 or 4, got " << pos.size() << ")" << std::endl;

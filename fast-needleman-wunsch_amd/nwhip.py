@@ -40,7 +40,9 @@ EXPORTS = ["nw_params_default", "nw_strerror", "nw_version", "nw_fill", "nw_tabl
            "nw_fill_band_cycle_async", "nw_fill_tband_async", "nw_link_wait_ctx_async", "nw_debug_failure",
            "nw_traceback", "nw_align", "nw_ops_expand", "nw_ops_score", "nw_ckpt_plan", "nw_ckpt_bytes", "nw_ckpt_peak_bytes",
            "nw_ckpt_sweep_async", "nw_score", "nw_traceback_block", "nw_align_ckpt", "nw_debug_tb_shift",
-           "nw_batch_dir_bytes", "nw_score_batch_async", "nw_score_batch", "nw_align_batch"]
+           "nw_batch_dir_bytes", "nw_score_batch_async", "nw_score_batch", "nw_align_batch",
+           "nw_batch_affine_dir_bytes", "nw_score_batch_affine_async", "nw_score_batch_affine",
+           "nw_align_batch_affine", "nw_ops_score_affine"]
 IPC_HANDLE_BYTES = 64
 
 
@@ -215,6 +217,20 @@ def lib() -> ctypes.CDLL:
     L.nw_align_batch.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams),
                                  ctypes.POINTER(NwBatchOpts), _i32p, _u8p, _i64p_, _i64p_,
                                  ctypes.POINTER(NwBatchStats)]
+    L.nw_batch_affine_dir_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
+    L.nw_batch_affine_dir_bytes.restype = ctypes.c_int64
+    L.nw_score_batch_affine_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.POINTER(NwParams), ctypes.c_int32,
+                                              ctypes.c_void_p, ctypes.c_void_p]
+    L.nw_score_batch_affine.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams),
+                                        ctypes.c_int32, _i32p, ctypes.POINTER(NwBatchStats)]
+    L.nw_align_batch_affine.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams),
+                                        ctypes.c_int32, ctypes.POINTER(NwBatchOpts), _i32p, _u8p, _i64p_, _i64p_,
+                                        ctypes.POINTER(NwBatchStats)]
+    L.nw_ops_score_affine.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                      _u8p, ctypes.c_int64, ctypes.POINTER(NwParams), ctypes.c_int32,
+                                      ctypes.POINTER(ctypes.c_int64)]
     L.nw_debug_tb_shift.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                     ctypes.c_int64]
     L.nw_debug_tb_shift.restype = ctypes.c_int64
@@ -490,6 +506,70 @@ def align_batch(pairs, scheme=(1, 0, -1), mem_bytes: int = 0, waves: int = 0, de
         raise NwError(st, "nw_align_batch")
     out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
     return scores[:n], out, stats
+
+
+def batch_affine_dir_bytes(n1: int, n2: int) -> int:
+    """Direction bytes of one pair in align_batch_affine (nw_batch_affine_dir_bytes): 4 bits
+    per cell, twice batch_dir_bytes; 0 for an empty side, -1 for a negative size."""
+    return int(lib().nw_batch_affine_dir_bytes(int(n1), int(n2)))
+
+
+def score_batch_affine(pairs, scheme=(1, 0, -1), gap_open: int = 0, waves: int = 0, device: int = -1,
+                       flags: int = 0, return_stats: bool = False):
+    """score_batch under affine gap cost (nw_score_batch_affine): a run of L ups or of L
+    lefts costs gap_open + L * scheme[2]."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    n = len(pairs)
+    scores = np.zeros(max(n, 1), np.int32)
+    stats = NwBatchStats()
+    p = params(scheme, waves, device, flags=flags)
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_score_batch_affine(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
+                                     off2.ctypes.data_as(i64p), n, ctypes.byref(p), int(gap_open),
+                                     scores.ctypes.data_as(_i32p), ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_score_batch_affine")
+    return (scores[:n], stats) if return_stats else scores[:n]
+
+
+def align_batch_affine(pairs, scheme=(1, 0, -1), gap_open: int = 0, mem_bytes: int = 0, waves: int = 0,
+                       device: int = -1, flags: int = 0):
+    """align_batch under affine gap cost (nw_align_batch_affine): (scores, [ops of pair 0,
+    ..], NwBatchStats), the ops the three-state walk include/nw_hip.h defines."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    n = len(pairs)
+    ops_off = off1 + off2
+    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
+    scores = np.zeros(max(n, 1), np.int32)
+    n_ops = np.zeros(max(n, 1), np.int64)
+    stats = NwBatchStats()
+    p = params(scheme, waves, device, flags=flags)
+    o = NwBatchOpts(int(mem_bytes))
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_align_batch_affine(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
+                                     off2.ctypes.data_as(i64p), n, ctypes.byref(p), int(gap_open), ctypes.byref(o),
+                                     scores.ctypes.data_as(_i32p),
+                                     ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                     ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_align_batch_affine")
+    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
+    return scores[:n], out, stats
+
+
+def ops_score_affine(s1, s2, ops, scheme=(1, 0, -1), gap_open: int = 0, begin=(0, 0)) -> int:
+    """Score of an alignment's ops under affine gap cost (nw_ops_score_affine): ops_score
+    plus gap_open for every run of ups or of lefts."""
+    a, b = _seq(s1), _seq(s2)
+    o = np.ascontiguousarray(np.asarray(ops, dtype=np.uint8))
+    p = params(scheme)
+    sc = ctypes.c_int64()
+    st = lib().nw_ops_score_affine(a.ctypes.data_as(_i8p), a.size, b.ctypes.data_as(_i8p), b.size, int(begin[0]),
+                                   int(begin[1]), o.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), o.size,
+                                   ctypes.byref(p), int(gap_open), ctypes.byref(sc))
+    if st != NW_OK:
+        raise NwError(st, "nw_ops_score_affine")
+    return int(sc.value)
 
 
 def ops_expand(s1, s2, ops, begin=(0, 0)):
@@ -1032,12 +1112,13 @@ class Context:
         return int(sc.item()), (gran & 0xFFFFFFFF).to(torch.int32)
 
     def score_batch(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, scheme=(1, 0, -1), stream=None,
-                    waves: int = 0, flags: int = 0):
+                    waves: int = 0, flags: int = 0, gap_open=None):
         """Scores of a batch on device tensors (nw_score_batch_async): d_s1cat / d_s2cat
         int8/uint8 CUDA tensors (the concatenations), d_off1 / d_off2 int64 CUDA tensors of
         npairs + 1 offsets, max_n2 >= every pair's n2.  Returns an int32 CUDA tensor of
         npairs scores, ordered on `stream` (default: torch's current stream); nothing is
-        synchronised.  Pairs are claimed in index order: submit them longest first."""
+        synchronised.  Pairs are claimed in index order: submit them longest first.
+        gap_open (an int): affine gap cost, see score_batch_affine (Context.score_batch_affine)."""
         import torch
         npairs = int(d_off1.numel()) - 1
         assert d_off1.dtype == torch.int64 and d_off2.dtype == torch.int64 and int(d_off2.numel()) == npairs + 1
@@ -1048,15 +1129,24 @@ class Context:
         with torch.cuda.stream(stream):
             scores = torch.zeros(max(npairs, 1), dtype=torch.int32, device=d_off1.device)
         p = params(scheme, waves, self.device, flags)
-        st = lib().nw_score_batch_async(self._h, ctypes.c_void_p(d_s1cat.data_ptr() if t1 else 0),
-                                        ctypes.c_void_p(d_off1.data_ptr()),
-                                        ctypes.c_void_p(d_s2cat.data_ptr() if t2 else 0),
-                                        ctypes.c_void_p(d_off2.data_ptr()), npairs, t1, t2, int(max_n2),
-                                        ctypes.byref(p), ctypes.c_void_p(scores.data_ptr()),
-                                        ctypes.c_void_p(stream.cuda_stream))
+        head = (self._h, ctypes.c_void_p(d_s1cat.data_ptr() if t1 else 0), ctypes.c_void_p(d_off1.data_ptr()),
+                ctypes.c_void_p(d_s2cat.data_ptr() if t2 else 0), ctypes.c_void_p(d_off2.data_ptr()), npairs, t1, t2,
+                int(max_n2), ctypes.byref(p))
+        tail = (ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(stream.cuda_stream))
+        if gap_open is None:
+            st, what = lib().nw_score_batch_async(*head, *tail), "nw_score_batch_async"
+        else:
+            st, what = lib().nw_score_batch_affine_async(*head, int(gap_open), *tail), "nw_score_batch_affine_async"
         if st != NW_OK:
-            raise NwError(st, "nw_score_batch_async")
+            raise NwError(st, what)
         return scores[:npairs]
+
+    def score_batch_affine(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, scheme=(1, 0, -1), gap_open: int = 0,
+                           stream=None, waves: int = 0, flags: int = 0):
+        """score_batch under affine gap cost (nw_score_batch_affine_async): a run of L ups
+        or of L lefts costs gap_open + L * scheme[2]."""
+        return self.score_batch(d_s1cat, d_off1, d_s2cat, d_off2, max_n2, scheme, stream, waves, flags,
+                                gap_open=int(gap_open))
 
     def traceback_block(self, d_s1, d_s2_block, table, row0: int, scheme=(1, 0, -1), stream=None, band: int = 0,
                         max_windows: int = 0, no_aim: bool = False):

@@ -469,6 +469,51 @@ int nw_align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat
                    int64_t npairs, const nw_params *p, const nw_batch_opts *o, int32_t *scores, uint8_t *ops,
                    const int64_t *ops_off, int64_t *n_ops, nw_batch_stats *stats);
 
+/* Batched global alignment under affine gap cost (Gotoh) ------------------------
+ * A run of L consecutive ups, or of L consecutive lefts, costs gap_open + L *
+ * gap_extend; an up-run directly followed by a left-run is two gaps.  gap_extend is
+ * nw_params.gap, gap_open the extra argument (gap_open = 0 is the linear cost, and
+ * then scores and ops are those of the linear entries).
+ *   E[i][j] = max(E[i][j-1] + ge, H[i][j-1] + go + ge)      (a left run ends at (i, j))
+ *   F[i][j] = max(F[i-1][j] + ge, H[i-1][j] + go + ge)      (an up run ends at (i, j))
+ *   H[i][j] = max(H[i-1][j-1] + s(s1[j-1], s2[i-1]), F[i][j], E[i][j])
+ *   H[0][0] = 0, H[0][j] = go + j*ge, H[i][0] = go + i*ge, E[i][0] = F[0][j] = -inf
+ * score = H[n2][n1].  The ops are the walk of a machine of three states from (n2, n1)
+ * to (0, 0): in H on row 0 / column 0 it goes left / up; in H at an inner cell it
+ * takes the first of diag, F, E that equals H (diag: op 0; F, E: change state, no op);
+ * in F it emits op 1, moves up and returns to H when F[i][j] == H[i-1][j] + go + ge
+ * (opening wins a tie over extending), else stays; E likewise with op 2 and a move
+ * left.  Contracts, CSR layout, options, statistics, slot sizes (n1 + n2), chunking
+ * and the order of the refusals are those of the linear entries above (the kernels:
+ * csrc/nw_batch_affine.hip; a worker keeps two columns between strips, the
+ * directions are 4 bits per cell).  Also refused with NW_ERR_ARG: gap_open > 0 (the
+ * machine would open a new gap at every step and the ops would no longer determine
+ * the score), and a pair beyond the int32 range of the kernel's form -- it holds H, E
+ * and F minus ge*(i+j) next to a "minus infinity" of -2^29, and
+ *   3*|gap_open| + (max(|match|, |mismatch|, |gap|) + |gap|) * (n1 + n2 + 2) < 2^28
+ * keeps every one of them above -2^28 (the _async form checks it for n1 = 0, n2 =
+ * max_n2).  A pair with an empty side scores gap_open + gap * max(n1, n2) (0 for 0 x
+ * 0), ops all ups / all lefts. */
+
+/* Direction bytes of one pair in nw_align_batch_affine: 4 bits per cell, 2 *
+ * nw_batch_dir_bytes(n1, n2).  0 when a side is empty, -1 for a negative size.  Host
+ * only. */
+int64_t nw_batch_affine_dir_bytes(int64_t n1, int64_t n2);
+
+int nw_score_batch_affine_async(nw_ctx *ctx, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                                const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2,
+                                int64_t max_n2, const nw_params *p, int32_t gap_open, int32_t *d_scores,
+                                void *stream);
+
+int nw_score_batch_affine(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                          int64_t npairs, const nw_params *p, int32_t gap_open, int32_t *scores,
+                          nw_batch_stats *stats);
+
+int nw_align_batch_affine(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                          int64_t npairs, const nw_params *p, int32_t gap_open, const nw_batch_opts *o,
+                          int32_t *scores, uint8_t *ops, const int64_t *ops_off, int64_t *n_ops,
+                          nw_batch_stats *stats);
+
 /* Launch-only variant for timing loops: no synchronisation, no readback. */
 int nw_fill_device_async(nw_ctx *ctx, const int8_t *d_s1, int64_t n1,
                          const int8_t *d_s2, int64_t n2, const nw_params *p,
@@ -710,11 +755,17 @@ void nw_synth_bdna(uint64_t seed, int64_t n, int8_t *out);
  * above 2 and for ops that run past either sequence.
  * nw_ops_expand: the two gapped rows, n_ops bytes each (0 = gap, the .bdna
  *   convention): row1 from s1, row2 from s2.
- * nw_ops_score: the sum of match / mismatch / gap along the ops. */
+ * nw_ops_score: the sum of match / mismatch / gap along the ops.
+ * nw_ops_score_affine: the same sum under affine gap cost -- match / mismatch per op
+ *   0, gap per op 1 or 2, plus gap_open whenever an op 1 or 2 differs from the op
+ *   before it (the first op has none before it: a gap there opens a run). */
 int nw_ops_expand(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t begin_i,
                   int64_t begin_j, const uint8_t *ops, int64_t n_ops, int8_t *row1, int8_t *row2);
 int nw_ops_score(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t begin_i,
                  int64_t begin_j, const uint8_t *ops, int64_t n_ops, const nw_params *p, int64_t *score);
+int nw_ops_score_affine(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t begin_i,
+                        int64_t begin_j, const uint8_t *ops, int64_t n_ops, const nw_params *p, int32_t gap_open,
+                        int64_t *score);
 
 #ifdef __cplusplus
 }

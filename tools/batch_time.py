@@ -10,6 +10,12 @@ library's one-pair path, unchanged by the batch; its scores must equal the batch
   --shape 150 | 1000 | 8000 | mixed | all   one shape per process, so that a job can give
                                             each its own time limit; the JSON is merged
 
+  --gap-open G      the affine-gap entries instead (nw_score_batch_affine, nw_align_batch_affine;
+                    a gap of length L costs G + L * gap): per shape their times and GCUPS, the
+                    linear entries timed in the same process right before them, and the ratio
+                    of the two; no host loop (the one-pair entries have no affine form).
+                    Writes profiles/batch_affine_time.json; profiles/batch_time.json stays.
+
 The score kernel's yardstick is the checkpoint sweep's pace on one huge table
 (profiles/ckpt_time.json: 262144^2 in 20.62 ms); `fraction_of_sweep_pace` states it.
 """
@@ -35,8 +41,11 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--shape", default="all")
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--loop-reps", type=int, default=5)
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_time.json"))
+ap.add_argument("--gap-open", type=int, default=None)
+ap.add_argument("--out", default=None)
 args = ap.parse_args()
+if args.out is None:
+    args.out = os.path.join(ROOT, "profiles", "batch_time.json" if args.gap_open is None else "batch_affine_time.json")
 scheme = (1, 0, -1)
 med = statistics.median
 
@@ -55,6 +64,45 @@ def make_pairs(name):
     else:
         lens = np.tile([lo, hi], (npairs, 1))
     return [(rng.integers(1, 5, int(a)).astype(np.int8), rng.integers(1, 5, int(b)).astype(np.int8)) for a, b in lens]
+
+
+def time_entries(pairs, cells, score_f, align_f):
+    """(score entry, align entry, scores): medians of --reps calls after a warm-up each."""
+    score_f(pairs, return_stats=True)
+    rs = [wall(lambda: score_f(pairs, return_stats=True)) for _ in range(args.reps)]
+    scores = rs[0][1][0]
+    fill = med(r[1][1].fill_ms for r in rs)
+    se = {"fill_ms": round(fill, 3), "wall_ms": round(med(r[0] for r in rs), 3),
+          "gcups_kernel": round(cells / (fill * 1e6), 1), "workers": int(rs[0][1][1].waves)}
+    align_f(pairs)
+    ra = [wall(lambda: align_f(pairs)) for _ in range(args.reps)]
+    st = ra[0][1][2]
+    afill, awalk = med(r[1][2].fill_ms for r in ra), med(r[1][2].walk_ms for r in ra)
+    assert np.array_equal(ra[0][1][0], scores)
+    ae = {"fill_ms": round(afill, 3), "walk_ms": round(awalk, 3), "fill_walk_ms": round(afill + awalk, 3),
+          "wall_ms": round(med(r[0] for r in ra), 3), "gcups_kernel": round(cells / (afill * 1e6), 1),
+          "gcups_fill_walk": round(cells / ((afill + awalk) * 1e6), 1), "chunks": int(st.chunks),
+          "dir_bytes": int(st.dir_bytes), "peak_bytes": int(st.peak_bytes)}
+    return se, ae, scores
+
+
+def run_affine(name):
+    go = args.gap_open
+    pairs = make_pairs(name)
+    cells = sum(a.size * b.size for a, b in pairs)
+    e = {"shape": name, "pairs": len(pairs), "cells": int(cells), "gap_open": go,
+         "lengths": "uniform %d..%d" % SHAPES[name][1:] if name == "mixed" else "%d x %d" % SHAPES[name][1:]}
+    ls, la, _ = time_entries(pairs, cells, lambda p, **kw: nwhip.score_batch(p, scheme, **kw),
+                             lambda p: nwhip.align_batch(p, scheme))
+    s, a, _ = time_entries(pairs, cells, lambda p, **kw: nwhip.score_batch_affine(p, scheme, go, **kw),
+                           lambda p: nwhip.align_batch_affine(p, scheme, go))
+    e["linear_score_batch"], e["linear_align_batch"] = ls, la
+    e["score_batch_affine"], e["align_batch_affine"] = s, a
+    e["score_affine_over_linear"] = round(s["fill_ms"] / ls["fill_ms"], 2)
+    e["align_fill_affine_over_linear"] = round(a["fill_ms"] / la["fill_ms"], 2)
+    e["align_fill_walk_affine_over_linear"] = round(a["fill_walk_ms"] / la["fill_walk_ms"], 2)
+    print(json.dumps(e), flush=True)
+    return e
 
 
 def run(name):
@@ -101,7 +149,7 @@ if os.path.exists(args.out):
 rec.update({"device": torch.cuda.get_device_name(0), "library": nwhip.version(), "scheme": list(scheme),
             "reps": args.reps, "sweep_yardstick_gcups": round(SWEEP_GCUPS, 1)})
 for name in (list(SHAPES) if args.shape == "all" else [args.shape]):
-    rec["shapes"][name] = run(name)
+    rec["shapes"][name] = run(name) if args.gap_open is None else run_affine(name)
 os.makedirs(os.path.dirname(args.out), exist_ok=True)
 with open(args.out, "w") as f:
     json.dump(rec, f, indent=1)
