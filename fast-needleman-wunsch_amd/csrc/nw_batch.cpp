@@ -4,8 +4,13 @@
 // that fit the device budget).  The affine-gap entries (nw_score_batch_affine_async,
 // nw_score_batch_affine, nw_align_batch_affine; kernels in nw_batch_affine.hip) are
 // the same three bodies: a Cost tells them which kernels to launch and that a worker's
-// column scratch and a pair's direction bytes are twice the linear ones.
+// column scratch and a pair's direction bytes are twice the linear ones.  The matrix
+// entries (nw_score_batch_matrix_async, nw_score_batch_matrix, nw_align_batch_matrix;
+// kernels in nw_batch_matrix.hip) are the affine ones with the substitution read from an
+// nw_submat: the Cost carries the matrix, batch_prepare maps the rows through its index
+// instead of running the charmap, and batch_run launches the matrix sweep.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <numeric>
 #include <vector>
@@ -17,10 +22,14 @@ using namespace nwh;
 
 namespace {
 
-// the gap cost of a call: linear (L * gap) or affine (open + L * gap)
+// the gap cost of a call: linear (L * gap) or affine (open + L * gap); the
+// substitution: match / mismatch, or a matrix
 struct Cost {
     bool affine = false;
     int32_t open = 0;
+    bool matrix = false;  // substitution by *mat (affine is then true): matrix_cost()
+    const nw_submat *mat = nullptr;
+    int64_t mat_abs = 0;  // max |score[x][y]| over x, y < n
     int64_t col_words(int64_t max_n2) const { return nw::batch_col_words(max_n2) * (affine ? 2 : 1); }
     int64_t dir_bytes(int64_t n1, int64_t n2) const {
         return affine ? nw_batch_affine_dir_bytes(n1, n2) : nw_batch_dir_bytes(n1, n2);
@@ -28,9 +37,53 @@ struct Cost {
     // a pair without cells: one run along the boundary
     int32_t empty_score(const nw_params *p, int64_t n) const { return (int32_t)((n > 0 ? open : 0) + p->gap * n); }
     bool range_ok(const nw_params *p, int64_t n1, int64_t i_max) const {
+        if (matrix) return matrix_range_ok(p, open, mat_abs, n1, i_max);
         return affine ? affine_range_ok(p, open, n1, i_max) : w_range_ok(p, n1, i_max);
     }
 };
+
+// a matrix the kernels can index without a bounds test: n letters, every byte mapped
+// to one of them
+bool valid_submat(const nw_submat *m) {
+    if (!m || m->n < 1 || m->n > NW_SUBMAT_MAX) return false;
+    for (int k = 0; k < 3; ++k)
+        if (m->reserved[k] != 0) return false;
+    for (int b = 0; b < 256; ++b)
+        if (m->index[b] >= m->n) return false;
+    return true;
+}
+
+Cost matrix_cost(const nw_submat *m, int32_t gap_open) {
+    Cost c{true, gap_open, true, m};
+    if (valid_submat(m))  // (an invalid one is refused by params_check before the range is looked at)
+        for (int x = 0; x < m->n; ++x)
+            for (int y = 0; y < m->n; ++y)
+                c.mat_abs = std::max<int64_t>(c.mat_abs, std::abs((int)m->score[x * NW_SUBMAT_MAX + y]));
+    return c;
+}
+
+// The matrix into the launch's arguments.  The cells hold the w form, which adds s - 2
+// gap per diagonal: those bytes when every one of them fits int8 (the kernel then adds
+// nothing), else s itself and the kernel adds -2 gap per cell (wide).  Entries beyond n
+// are 0 whatever the caller left there.
+void submat_args(const nw_submat *m, int32_t gap, nw::BatchMatrixArgs *ma) {
+    bool fits = true;
+    for (int x = 0; x < m->n && fits; ++x)
+        for (int y = 0; y < m->n; ++y) {
+            const int v = (int)m->score[x * NW_SUBMAT_MAX + y] - 2 * gap;
+            if (v < -128 || v > 127) fits = false;
+        }
+    int8_t bytes[NW_SUBMAT_MAX * NW_SUBMAT_MAX];
+    std::memset(bytes, 0, sizeof bytes);
+    for (int x = 0; x < m->n; ++x)
+        for (int y = 0; y < m->n; ++y)
+            bytes[x * NW_SUBMAT_MAX + y] = (int8_t)(m->score[x * NW_SUBMAT_MAX + y] - (fits ? 2 * gap : 0));
+    static_assert(sizeof bytes == sizeof ma->score && NW_SUBMAT_MAX == nw::kBatchMatrixLetters, "nw_submat layout");
+    std::memcpy(ma->score, bytes, sizeof bytes);
+    std::memcpy(ma->index, m->index, 256);
+    ma->n = m->n;
+    ma->wide = fits ? 0 : 1;
+}
 
 // what every batch entry refuses in its parameters, judged without a device
 // (NW_KERNEL_PANELS, which is NW_ERR_UNSUPPORTED, comes after every NW_ERR_ARG)
@@ -41,6 +94,7 @@ int params_check(const nw_params *p, int64_t npairs, const Cost &cost) {
     // would no longer determine the score
     if (cost.affine && cost.open > 0) return NW_ERR_ARG;
     if (npairs < 0 || npairs >= INT32_MAX) return NW_ERR_ARG;
+    if (cost.matrix && !valid_submat(cost.mat)) return NW_ERR_ARG;
     return NW_OK;
 }
 
@@ -79,12 +133,13 @@ void batch_order(const int64_t *off1, const int64_t *off2, int64_t npairs, Batch
 
 // The context's workspace of a batch launch, the charmap over the concatenated s1 and
 // the row characters of the concatenated s2 (three small launches per batch, whatever
-// its number of pairs); *a gets everything but the tickets, the scores and the
+// its number of pairs; with a matrix: one launch, the rows as letters, and the matrix
+// into *ma); *ma gets everything but the tickets, the scores and the
 // directions, *grid the workers (nw_params.waves; 0: kCkptWavesPerCU per CU) capped at
 // `tickets`.
 int batch_prepare(nw_ctx *c, const int8_t *d_s1, const int64_t *d_off1, int64_t total1, const int8_t *d_s2,
                   const int64_t *d_off2, int64_t total2, int64_t max_n2, const nw_params *p, const Cost &cost,
-                  int64_t tickets, void *stream, nw::BatchAffineArgs *aa, int *grid) {
+                  int64_t tickets, void *stream, nw::BatchMatrixArgs *ma, int *grid) {
     int st;
     int64_t waves = p->waves > 0 ? p->waves : (int64_t)c->cus * nw::kCkptWavesPerCU;
     waves = std::max<int64_t>(1, std::min<int64_t>(waves, tickets));
@@ -92,12 +147,21 @@ int batch_prepare(nw_ctx *c, const int8_t *d_s1, const int64_t *d_off1, int64_t 
     const int64_t rows_len = nw::kBatchRowPad + total2 + nw::kBatchRowTail;
     if ((st = grow((void **)&c->rowpack, &c->rowpack_cap, (size_t)rows_len)) != NW_OK) return st;
     if ((st = grow((void **)&c->scratch, &c->scratch_cap, (size_t)(waves * cstride) * 4)) != NW_OK) return st;
-    const bool perm_ok = perm_allowed(p, 2 * p->gap);
-    if (nw::launch_charmap((const uint8_t *)d_s1, total1, c->meta, stream) != hipSuccess) return NW_ERR_HIP;
-    if (nw::launch_batch_rows((const uint8_t *)d_s2, total2, perm_ok ? 1 : 0, c->meta, (uint8_t *)c->rowpack,
-                              stream) != hipSuccess)
-        return NW_ERR_HIP;
-    std::memset(aa, 0, sizeof *aa);
+    const bool perm_ok = !cost.matrix && perm_allowed(p, 2 * p->gap);
+    std::memset(ma, 0, sizeof *ma);
+    nw::BatchAffineArgs *aa = &ma->a;
+    if (cost.matrix) {
+        // the matrix is the alphabet: no charmap pass, the rows become letters
+        if (nw::launch_batch_matrix_rows((const uint8_t *)d_s2, total2, cost.mat->index, (uint8_t *)c->rowpack,
+                                         stream) != hipSuccess)
+            return NW_ERR_HIP;
+        submat_args(cost.mat, p->gap, ma);
+    } else {
+        if (nw::launch_charmap((const uint8_t *)d_s1, total1, c->meta, stream) != hipSuccess) return NW_ERR_HIP;
+        if (nw::launch_batch_rows((const uint8_t *)d_s2, total2, perm_ok ? 1 : 0, c->meta, (uint8_t *)c->rowpack,
+                                  stream) != hipSuccess)
+            return NW_ERR_HIP;
+    }
     aa->gap_open = cost.open;
     aa->eoff = nw::batch_col_words(max_n2);
     nw::BatchArgs *a = &aa->b;
@@ -120,10 +184,13 @@ int batch_prepare(nw_ctx *c, const int8_t *d_s1, const int64_t *d_off1, int64_t 
 }
 
 // one launch of the batch kernel over a->npairs tickets
-int batch_run(nw_ctx *c, const nw::BatchAffineArgs &aa, const Cost &cost, bool dirs, int grid, void *stream) {
+int batch_run(nw_ctx *c, const nw::BatchMatrixArgs &ma, const Cost &cost, bool dirs, int grid, void *stream) {
     if (nw::launch_ctrl_reset(c->ctrl, stream) != hipSuccess) return NW_ERR_HIP;
+    const nw::BatchAffineArgs &aa = ma.a;
     const int g = std::min(grid, std::max(aa.b.npairs, 1));
-    const int e = cost.affine ? nw::launch_batch_affine(aa, dirs, g, stream) : nw::launch_batch(aa.b, dirs, g, stream);
+    const int e = cost.matrix   ? nw::launch_batch_matrix(ma, dirs, g, stream)
+                  : cost.affine ? nw::launch_batch_affine(aa, dirs, g, stream)
+                                : nw::launch_batch(aa.b, dirs, g, stream);
     if (e != hipSuccess) return NW_ERR_HIP;
     c->last_waves = grid;
     c->last_kernel = NW_KERNEL_STRIPS;
@@ -181,14 +248,14 @@ int score_batch_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, c
     if (npairs == 0) return NW_OK;
     if (!d_off1 || !d_off2 || !d_scores || (total1 > 0 && !d_s1cat) || (total2 > 0 && !d_s2cat)) return NW_ERR_ARG;
     NW_HIP_TRY(hipSetDevice(c->device));
-    nw::BatchAffineArgs aa;
+    nw::BatchMatrixArgs ma;
     int grid = 0;
-    if ((st = batch_prepare(c, d_s1cat, d_off1, total1, d_s2cat, d_off2, total2, max_n2, p, cost, npairs, stream, &aa,
+    if ((st = batch_prepare(c, d_s1cat, d_off1, total1, d_s2cat, d_off2, total2, max_n2, p, cost, npairs, stream, &ma,
                             &grid)) != NW_OK)
         return st;
-    aa.b.npairs = (int32_t)npairs;  // (tickets in index order: the lengths are on the device)
-    aa.b.scores = d_scores;
-    return batch_run(c, aa, cost, false, grid, stream);
+    ma.a.b.npairs = (int32_t)npairs;  // (tickets in index order: the lengths are on the device)
+    ma.a.b.scores = d_scores;
+    return batch_run(c, ma, cost, false, grid, stream);
 }
 
 int score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2, int64_t npairs,
@@ -225,16 +292,16 @@ int score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
     DevBufs bufs;
     BatchDev d;
     if ((st = d.upload(bufs, s1cat, off1, s2cat, off2, npairs, b)) != NW_OK) return st;
-    nw::BatchAffineArgs aa;
+    nw::BatchMatrixArgs ma;
     int grid = 0;
-    if ((st = batch_prepare(c, d.s1, d.off1, b.total1, d.s2, d.off2, b.total2, b.max_n2, p, cost, cnt, nullptr, &aa,
+    if ((st = batch_prepare(c, d.s1, d.off1, b.total1, d.s2, d.off2, b.total2, b.max_n2, p, cost, cnt, nullptr, &ma,
                             &grid)) != NW_OK)
         return st;
-    aa.b.order = d.order;
-    aa.b.npairs = (int32_t)cnt;
-    aa.b.scores = d.scores;
+    ma.a.b.order = d.order;
+    ma.a.b.npairs = (int32_t)cnt;
+    ma.a.b.scores = d.scores;
     NW_HIP_TRY(hipEventRecord(c->ev0, nullptr));
-    if ((st = batch_run(c, aa, cost, false, grid, nullptr)) != NW_OK) return st;
+    if ((st = batch_run(c, ma, cost, false, grid, nullptr)) != NW_OK) return st;
     NW_HIP_TRY(hipEventRecord(c->ev1, nullptr));
     std::vector<int32_t> got((size_t)npairs);
     NW_HIP_TRY(hipMemcpy(got.data(), d.scores, (size_t)npairs * 4, hipMemcpyDeviceToHost));
@@ -350,10 +417,10 @@ int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
     NW_HIP_TRY(hipEventCreate(&ef.a));
     NW_HIP_TRY(hipEventCreate(&ef.b));
     NW_HIP_TRY(hipEventCreate(&ew.b));
-    nw::BatchAffineArgs aa;
-    nw::BatchArgs &a = aa.b;
+    nw::BatchMatrixArgs ma;
+    nw::BatchArgs &a = ma.a.b;
     int grid = 0;
-    if ((st = batch_prepare(c, d.s1, d.off1, b.total1, d.s2, d.off2, b.total2, b.max_n2, p, cost, cnt, nullptr, &aa,
+    if ((st = batch_prepare(c, d.s1, d.off1, b.total1, d.s2, d.off2, b.total2, b.max_n2, p, cost, cnt, nullptr, &ma,
                             &grid)) != NW_OK)
         return st;
     a.scores = d.scores;
@@ -375,7 +442,7 @@ int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
         w.ops_off = d_loc_off + t0;
         w.n_ops = d_nops + t0;
         NW_HIP_TRY(hipEventRecord(ef.a, nullptr));
-        if ((st = batch_run(c, aa, cost, true, grid, nullptr)) != NW_OK) return st;
+        if ((st = batch_run(c, ma, cost, true, grid, nullptr)) != NW_OK) return st;
         NW_HIP_TRY(hipEventRecord(ef.b, nullptr));
         if ((cost.affine ? nw::launch_batch_affine_walk(w, nullptr) : nw::launch_batch_walk(w, nullptr)) != hipSuccess)
             return NW_ERR_HIP;
@@ -463,6 +530,28 @@ int nw_align_batch_affine(const int8_t *s1cat, const int64_t *off1, const int8_t
                           nw_batch_stats *stats) {
     return align_batch(s1cat, off1, s2cat, off2, npairs, p, Cost{true, gap_open}, o, scores, ops, ops_off, n_ops,
                        stats);
+}
+
+int nw_score_batch_matrix_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                                const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2,
+                                int64_t max_n2, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                                int32_t *d_scores, void *stream) {
+    return score_batch_async(c, d_s1cat, d_off1, d_s2cat, d_off2, npairs, total1, total2, max_n2, p,
+                             matrix_cost(m, gap_open), d_scores, stream);
+}
+
+int nw_score_batch_matrix(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                          int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t *scores,
+                          nw_batch_stats *stats) {
+    return score_batch(s1cat, off1, s2cat, off2, npairs, p, matrix_cost(m, gap_open), scores, stats);
+}
+
+int nw_align_batch_matrix(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                          int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                          const nw_batch_opts *o, int32_t *scores, uint8_t *ops, const int64_t *ops_off,
+                          int64_t *n_ops, nw_batch_stats *stats) {
+    return align_batch(s1cat, off1, s2cat, off2, npairs, p, matrix_cost(m, gap_open), o, scores, ops, ops_off,
+                       n_ops, stats);
 }
 
 }  // extern "C"

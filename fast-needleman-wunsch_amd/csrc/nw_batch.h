@@ -66,6 +66,19 @@ struct BatchAffineArgs {
     int64_t eoff;
 };
 
+// The matrix kernels (nw_batch_matrix.hip): the affine launch's arguments (a.b.match,
+// mismatch, perm, charmap and nprof unused; a.b.rows holds LETTERS, launch_batch_matrix_
+// rows) and the substitution matrix itself -- no device buffer, no copy.
+constexpr int kBatchMatrixLetters = 32;  // NW_SUBMAT_MAX
+struct BatchMatrixArgs {
+    BatchAffineArgs a;
+    int32_t n;     // letters, 1 .. kBatchMatrixLetters
+    int32_t wide;  // 0: score holds s - 2 * gap (every one fits int8); 1: s, and the cell adds -2 * gap
+    // dword [x * 8 + g], byte b: the score byte of (s1 letter x, s2 letter 4g + b); 0 beyond n
+    alignas(16) uint32_t score[kBatchMatrixLetters * kBatchMatrixLetters / 4];
+    uint8_t index[256];  // byte -> letter < n
+};
+
 // mapped (perm and at most kMaxPerm distinct column characters) or raw copy of s2cat
 int launch_batch_rows(const uint8_t *d_s2, int64_t total2, int32_t perm, const uint8_t *meta, uint8_t *d_rows,
                       void *stream);
@@ -75,5 +88,10 @@ int launch_batch_walk(const BatchWalkArgs &w, void *stream);
 // the same two for affine gaps: the walk is a machine of three states over 4 bits per cell
 int launch_batch_affine(const BatchAffineArgs &a, bool dirs, int grid, void *stream);
 int launch_batch_affine_walk(const BatchWalkArgs &w, void *stream);
+// substitution by matrix: d_rows[kBatchRowPad + i] = index[s2cat[i]] between zeroed pads;
+// the sweep (its directions are the affine kernel's: launch_batch_affine_walk walks them)
+int launch_batch_matrix_rows(const uint8_t *d_s2, int64_t total2, const uint8_t *index, uint8_t *d_rows,
+                             void *stream);
+int launch_batch_matrix(const BatchMatrixArgs &a, bool dirs, int grid, void *stream);
 
 }  // namespace nw

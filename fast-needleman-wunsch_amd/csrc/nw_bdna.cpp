@@ -117,4 +117,24 @@ int nw_ops_score_affine(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t 
     return st;
 }
 
+int nw_ops_score_matrix(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t begin_i, int64_t begin_j,
+                        const uint8_t *ops, int64_t n_ops, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                        int64_t *score) {
+    if (!p || !score || !m || m->n < 1 || m->n > NW_SUBMAT_MAX) return NW_ERR_ARG;
+    if (m->reserved[0] != 0 || m->reserved[1] != 0 || m->reserved[2] != 0) return NW_ERR_ARG;
+    for (int b = 0; b < 256; ++b)
+        if (m->index[b] >= m->n) return NW_ERR_ARG;
+    int64_t sum = 0;
+    uint8_t prev = 0;  // (a diag: the first gap op opens a run)
+    const int st = walk_ops(s1, n1, s2, n2, begin_i, begin_j, ops, n_ops, [&](int64_t, uint8_t op, int64_t i, int64_t j) {
+        if (op != 0)
+            sum += p->gap + (op != prev ? gap_open : 0);
+        else
+            sum += m->score[m->index[(uint8_t)s1[j]] * NW_SUBMAT_MAX + m->index[(uint8_t)s2[i]]];
+        prev = op;
+    });
+    if (st == NW_OK) *score = sum;
+    return st;
+}
+
 }  // extern "C"

@@ -110,6 +110,7 @@ int tb_args(int64_t n1, int64_t n2, const nw_params *p, const nw_tb_opts *o, con
 // ---- nw_launch.cpp: what every strip-chain launch shares
 bool w_range_ok(const nw_params *p, int64_t n1, int64_t i_max);
 bool affine_range_ok(const nw_params *p, int32_t gap_open, int64_t n1, int64_t i_max);
+bool matrix_range_ok(const nw_params *p, int32_t gap_open, int64_t max_abs, int64_t n1, int64_t i_max);
 bool perm_allowed(const nw_params *p, int32_t off);
 int launch_workspace(nw_ctx *c, const Shape &s, uint64_t ntags, int32_t nbl, void *stream, int64_t *qlen);
 // ---- nw_hostpath.cpp: the one-shot entries' device and its kept context, held

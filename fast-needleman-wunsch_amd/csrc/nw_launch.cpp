@@ -43,6 +43,14 @@ bool affine_range_ok(const nw_params *p, int32_t gap_open, int64_t n1, int64_t i
     return 3 * std::llabs((long long)gap_open) + (m + std::llabs(p->gap)) * (long long)(n1 + i_max + 2) < (1LL << 28);
 }
 
+// The matrix kernels are the affine ones with s read from an int8 matrix: the bound is
+// affine_range_ok's with the matrix's largest |entry| (max_abs, over the n letters) in
+// the place of match / mismatch.  Nothing else in the argument above depends on s.
+bool matrix_range_ok(const nw_params *p, int32_t gap_open, int64_t max_abs, int64_t n1, int64_t i_max) {
+    const long long m = std::max<long long>(max_abs, std::llabs(p->gap));
+    return 3 * std::llabs((long long)gap_open) + (m + std::llabs(p->gap)) * (long long)(n1 + i_max + 2) < (1LL << 28);
+}
+
 // v_perm score tables when every substitution score minus `off` fits int8 (the
 // kernel falls back to compares on the device when s1 holds more than kMaxPerm
 // distinct characters).  off: the table bytes are s - 2 GAP in the w form (NW, and

@@ -7,13 +7,21 @@
 //   --mem BYTES / --block-rows K: align in linear memory (nw_align_ckpt) within BYTES
 //   of device memory / in blocks of K rows (a multiple of 64); the output is the same.
 //   --score-only: no alignment, the score from the table-free sweep (nw_score).
-//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only] [--gap-open G]
+//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only] [--gap-open G] [--matrix FILE]
 //   LIST: a text file, one pair "A.bdna B.bdna" per line (paths relative to the
 //   list's directory unless absolute); all pairs are aligned in ONE call
 //   (nw_align_batch; --score-only: nw_score_batch).  stdout: "<ms>\n", then one
 //   "Score: <t[n2][n1]>" line per pair, in the list's order.
 //   --gap-open G (G <= 0, with --batch only): affine gap cost, a gap of length L costs
 //   G + L * g (nw_align_batch_affine / nw_score_batch_affine).
+//   --matrix FILE (with --batch only): substitution by matrix (nw_align_batch_matrix /
+//   nw_score_batch_matrix); --scheme's third number is the gap extension, --gap-open the
+//   opening (default 0).  FILE is the usual NCBI text layout: '#' comment lines, a header
+//   row of letters, one row per letter (the letter, then one integer in -128..127 per
+//   header letter); the entry of row r, column c scores an A letter r against a B letter
+//   c.  A letter is one character or 0xHH (a byte value); a lower-case byte maps like its
+//   upper-case letter; with a '*' among the letters every unlisted byte maps to it,
+//   without one an unlisted byte in a sequence is an error.
 // Argument and missing-file errors are nw_driver's (exit 1); a device failure is
 // reported on stderr and exits 2.
 #include <chrono>
@@ -35,8 +43,93 @@ static bool write_file(const char *path, const std::vector<int8_t> &row) {
     return std::fclose(f) == 0 && ok;
 }
 
+// a letter of a matrix file: one character, or 0xHH
+static int letter_byte(const std::string &t) {
+    if (t.size() == 1) return (unsigned char)t[0];
+    if (t.size() == 4 && t[0] == '0' && (t[1] == 'x' || t[1] == 'X')) {
+        char *end = nullptr;
+        const long v = std::strtol(t.c_str() + 2, &end, 16);
+        if (*end == 0 && v >= 0 && v <= 255) return (int)v;
+    }
+    return -1;
+}
+
+// --matrix FILE into *m; listed[b]: byte b is a letter (or the lower case of one).  The
+// format is nwhip.SubMatrix.from_text's.
+static bool read_matrix(const char *path, nw_submat *m, bool *listed, std::string *err) {
+    std::ifstream in(path);
+    if (!in) {
+        *err = std::string("ERROR: no such file ") + path;
+        return false;
+    }
+    std::memset(m, 0, sizeof *m);
+    std::vector<int> letters;
+    int pos[256];
+    bool have_row[NW_SUBMAT_MAX] = {false};
+    for (int b = 0; b < 256; ++b) pos[b] = -1;
+    std::string line;
+    size_t rows = 0;
+    while (std::getline(in, line)) {
+        std::istringstream ls(line);
+        std::vector<std::string> tok;
+        for (std::string t; ls >> t;) tok.push_back(t);
+        if (tok.empty() || tok[0][0] == '#') continue;
+        if (letters.empty()) {
+            for (const std::string &t : tok) {
+                const int b = letter_byte(t);
+                if (b < 0 || pos[b] >= 0 || letters.size() >= (size_t)NW_SUBMAT_MAX) {
+                    *err = "error: --matrix: the header must be 1..32 distinct letters (one character or 0xHH)";
+                    return false;
+                }
+                pos[b] = (int)letters.size();
+                letters.push_back(b);
+            }
+            continue;
+        }
+        const int r = letter_byte(tok[0]);
+        if (r < 0 || pos[r] < 0 || have_row[pos[r]] || tok.size() != letters.size() + 1) {
+            *err = "error: --matrix: row '" + line + "': a letter of the header and one number per letter expected";
+            return false;
+        }
+        for (size_t c = 0; c < letters.size(); ++c) {
+            char *end = nullptr;
+            const long v = std::strtol(tok[c + 1].c_str(), &end, 10);
+            if (*end != 0 || end == tok[c + 1].c_str() || v < -128 || v > 127) {
+                *err = "error: --matrix: row '" + line + "': integers in -128..127 expected";
+                return false;
+            }
+            m->score[pos[r] * NW_SUBMAT_MAX + (int)c] = (int8_t)v;
+        }
+        have_row[pos[r]] = true;
+        ++rows;
+    }
+    if (letters.empty() || rows != letters.size()) {
+        *err = "error: --matrix: a header row and one row per letter expected";
+        return false;
+    }
+    m->n = (int32_t)letters.size();
+    const int other = pos[(unsigned char)'*'];
+    for (int b = 0; b < 256; ++b) {
+        int k = pos[b];
+        if (k < 0 && b >= 'a' && b <= 'z') k = pos[b - 32];
+        listed[b] = k >= 0 || other >= 0;
+        m->index[b] = (uint8_t)(k >= 0 ? k : other >= 0 ? other : 0);
+    }
+    return true;
+}
+
 // --batch LIST: every pair of the list in one call
-static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bool score_only, const int32_t *gap_open) {
+static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bool score_only, const int32_t *gap_open,
+                     const char *matrix) {
+    nw_submat mat;
+    bool listed[256];
+    if (matrix != nullptr) {
+        std::string err;
+        if (!read_matrix(matrix, &mat, listed, &err)) {
+            std::cout << err << std::endl;
+            return 1;
+        }
+    }
     std::ifstream in(list);
     if (!in) {
         std::cout << "ERROR: no such file " << list << std::endl;
@@ -65,6 +158,13 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
                 std::cout << "ERROR: no such file " << path << std::endl;
                 return 1;
             }
+            if (matrix != nullptr)
+                for (int64_t x = 0; x < n; ++x)
+                    if (!listed[(unsigned char)s[x]]) {
+                        std::cout << "ERROR: byte " << (int)(unsigned char)s[x] << " of " << path
+                                  << " is not a letter of the matrix (list a '*' letter for such bytes)" << std::endl;
+                        return 1;
+                    }
             std::vector<int8_t> &cat = k == 0 ? s1cat : s2cat;
             cat.insert(cat.end(), s, s + n);
             (k == 0 ? off1 : off2).push_back((int64_t)cat.size());
@@ -81,7 +181,13 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
     bo.mem_bytes = mem_bytes;
     auto wallStart = std::chrono::system_clock::now();
     int st;
-    if (gap_open != nullptr)
+    if (matrix != nullptr)
+        st = score_only ? nw_score_batch_matrix(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
+                                                gap_open ? *gap_open : 0, scores.data(), nullptr)
+                        : nw_align_batch_matrix(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
+                                                gap_open ? *gap_open : 0, &bo, scores.data(), ops.data(),
+                                                ops_off.data(), n_ops.data(), nullptr);
+    else if (gap_open != nullptr)
         st = score_only ? nw_score_batch_affine(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p,
                                                 *gap_open, scores.data(), nullptr)
                         : nw_align_batch_affine(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p,
@@ -110,7 +216,7 @@ int main(int argc, char **argv) {
     nw_ckpt_opts co;
     std::memset(&co, 0, sizeof co);
     bool ckpt = false, score_only = false;
-    const char *batch = nullptr;
+    const char *batch = nullptr, *matrix = nullptr;
     int32_t gap_open = 0;
     bool affine = false;
     for (int a = 1; a < argc; ++a) {
@@ -142,6 +248,12 @@ int main(int argc, char **argv) {
             gap_open = g;
             affine = true;
             ++a;
+        } else if (std::strcmp(argv[a], "--matrix") == 0) {
+            if (a + 1 >= argc) {
+                std::cout << "error: --matrix expects a matrix file" << std::endl;
+                return 1;
+            }
+            matrix = argv[++a];
         } else if (std::strcmp(argv[a], "--score-only") == 0) {
             score_only = true;
         } else if (std::strcmp(argv[a], "--batch") == 0) {
@@ -156,11 +268,17 @@ int main(int argc, char **argv) {
     }
     if (batch != nullptr) {
         if (!pos.empty() || co.block_rows != 0) {
-            std::cout << "error: --batch takes the list alone (and --scheme, --mem, --score-only, --gap-open)"
+            std::cout << "error: --batch takes the list alone (and --scheme, --mem, --score-only, --gap-open, "
+                         "--matrix)"
                       << std::endl;
             return 1;
         }
-        return run_batch(batch, p, co.mem_bytes, score_only, affine ? &gap_open : nullptr);
+        return run_batch(batch, p, co.mem_bytes, score_only, affine ? &gap_open : nullptr, matrix);
+    }
+    if (matrix != nullptr) {
+        std::cout << "error: --matrix needs --batch (substitution matrices are built for the batched alignment only)"
+                  << std::endl;
+        return 1;
     }
     if (affine) {
         std::cout << "error: --gap-open needs --batch (affine gaps are built for the batched alignment only)"

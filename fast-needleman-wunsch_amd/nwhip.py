@@ -42,7 +42,8 @@ EXPORTS = ["nw_params_default", "nw_strerror", "nw_version", "nw_fill", "nw_tabl
            "nw_ckpt_sweep_async", "nw_score", "nw_traceback_block", "nw_align_ckpt", "nw_debug_tb_shift",
            "nw_batch_dir_bytes", "nw_score_batch_async", "nw_score_batch", "nw_align_batch",
            "nw_batch_affine_dir_bytes", "nw_score_batch_affine_async", "nw_score_batch_affine",
-           "nw_align_batch_affine", "nw_ops_score_affine"]
+           "nw_align_batch_affine", "nw_ops_score_affine",
+           "nw_score_batch_matrix_async", "nw_score_batch_matrix", "nw_align_batch_matrix", "nw_ops_score_matrix"]
 IPC_HANDLE_BYTES = 64
 
 
@@ -105,6 +106,15 @@ class NwBatchStats(ctypes.Structure):
     _fields_ = [("pairs", ctypes.c_int64), ("cells", ctypes.c_int64), ("chunks", ctypes.c_int64),
                 ("dir_bytes", ctypes.c_int64), ("peak_bytes", ctypes.c_int64), ("waves", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("fill_ms", ctypes.c_double), ("walk_ms", ctypes.c_double)]
+
+
+SUBMAT_MAX = 32  # NW_SUBMAT_MAX: letters of a substitution matrix
+
+
+class NwSubmat(ctypes.Structure):
+    """nw_submat (include/nw_hip.h): a substitution matrix over at most 32 letters."""
+    _fields_ = [("n", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3), ("index", ctypes.c_uint8 * 256),
+                ("score", ctypes.c_int8 * (SUBMAT_MAX * SUBMAT_MAX))]
 
 
 CKPT_TAG = 1   # NW_CKPT_TAG: the tag of every checkpoint granule (nw_band.tag of a re-fill)
@@ -230,6 +240,19 @@ def lib() -> ctypes.CDLL:
                                         ctypes.POINTER(NwBatchStats)]
     L.nw_ops_score_affine.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                       _u8p, ctypes.c_int64, ctypes.POINTER(NwParams), ctypes.c_int32,
+                                      ctypes.POINTER(ctypes.c_int64)]
+    _smp = ctypes.POINTER(NwSubmat)
+    L.nw_score_batch_matrix_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.POINTER(NwParams), _smp, ctypes.c_int32,
+                                              ctypes.c_void_p, ctypes.c_void_p]
+    L.nw_score_batch_matrix.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams), _smp,
+                                        ctypes.c_int32, _i32p, ctypes.POINTER(NwBatchStats)]
+    L.nw_align_batch_matrix.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams), _smp,
+                                        ctypes.c_int32, ctypes.POINTER(NwBatchOpts), _i32p, _u8p, _i64p_, _i64p_,
+                                        ctypes.POINTER(NwBatchStats)]
+    L.nw_ops_score_matrix.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                      _u8p, ctypes.c_int64, ctypes.POINTER(NwParams), _smp, ctypes.c_int32,
                                       ctypes.POINTER(ctypes.c_int64)]
     L.nw_debug_tb_shift.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                     ctypes.c_int64]
@@ -569,6 +592,179 @@ def ops_score_affine(s1, s2, ops, scheme=(1, 0, -1), gap_open: int = 0, begin=(0
                                    ctypes.byref(p), int(gap_open), ctypes.byref(sc))
     if st != NW_OK:
         raise NwError(st, "nw_ops_score_affine")
+    return int(sc.value)
+
+
+def _letter_byte(tok) -> int:
+    """A letter of a matrix: an int byte value, a one-character str / bytes, or "0xHH"."""
+    if isinstance(tok, (int, np.integer)):
+        v = int(tok)
+    elif isinstance(tok, bytes) and len(tok) == 1:
+        v = tok[0]
+    elif isinstance(tok, str) and len(tok) == 1:
+        v = ord(tok)
+    elif isinstance(tok, str) and len(tok) == 4 and tok[:2] in ("0x", "0X"):
+        v = int(tok[2:], 16)
+    else:
+        raise ValueError(f"matrix letter {tok!r}: one character or 0xHH expected")
+    if not 0 <= v <= 255:
+        raise ValueError(f"matrix letter {tok!r} is not a byte")
+    return v
+
+
+class SubMatrix:
+    """A substitution matrix for the *_matrix calls (nw_submat, include/nw_hip.h).
+
+    letters: n <= 32 distinct letters -- a str or bytes (one letter per character) or a
+             sequence of byte values / one-character strings / "0xHH" strings.
+    scores:  n x n integers that fit int8; scores[x][y] = s(s1 letter x, s2 letter y), so
+             the matrix may be asymmetric.
+    other:   the letter every unlisted byte maps to (a wildcard: X, N, *).  Without it an
+             unlisted byte in a sequence raises ValueError in the host-side calls, and
+             the device-side call (Context.score_batch_matrix), which cannot look at the
+             sequences, refuses the matrix.
+    A lower-case ASCII byte maps like its upper-case letter unless it is listed itself."""
+
+    def __init__(self, letters, scores, other=None):
+        if isinstance(letters, (str, bytes, bytearray)):
+            letters = list(letters)
+        self.letters = [_letter_byte(t) for t in letters]
+        n = len(self.letters)
+        if not 1 <= n <= SUBMAT_MAX:
+            raise ValueError(f"a matrix has 1..{SUBMAT_MAX} letters, not {n}")
+        if len(set(self.letters)) != n:
+            raise ValueError("matrix letters must be distinct")
+        sc = np.asarray(scores)
+        if sc.shape != (n, n) or not np.issubdtype(sc.dtype, np.integer):
+            raise ValueError(f"scores must be {n} x {n} integers")
+        if sc.min() < -128 or sc.max() > 127:
+            raise ValueError("matrix scores must fit int8 (-128..127)")
+        self.scores = sc.astype(np.int64)
+        self.other = None if other is None else _letter_byte(other)
+        if self.other is not None and self.other not in self.letters:
+            raise ValueError("other must be one of the letters")
+        pos = {b: k for k, b in enumerate(self.letters)}
+        fill = pos[self.other] if self.other is not None else 0
+        self.index = np.full(256, fill, np.uint8)
+        self.listed = np.zeros(256, bool)
+        for b, k in pos.items():
+            self.index[b], self.listed[b] = k, True
+        for b in range(ord("a"), ord("z") + 1):
+            if not self.listed[b] and self.listed[b - 32]:
+                self.index[b], self.listed[b] = self.index[b - 32], True
+        self.c = NwSubmat()
+        self.c.n = n
+        self.c.index[:] = self.index.tolist()
+        full = np.zeros((SUBMAT_MAX, SUBMAT_MAX), np.int8)
+        full[:n, :n] = sc
+        self.c.score[:] = full.ravel().tolist()
+
+    @property
+    def n(self) -> int:
+        return len(self.letters)
+
+    def check(self, *seqs) -> None:
+        """Without `other`: ValueError for a sequence byte that is no letter."""
+        if self.other is not None:
+            return
+        for s in seqs:
+            s = _seq(s).view(np.uint8)
+            bad = ~self.listed[s]
+            if bad.any():
+                raise ValueError(f"byte {int(s[bad][0])} is not a letter of the matrix (pass other=)")
+
+    @classmethod
+    def from_text(cls, path_or_str, other=None):
+        """The usual NCBI text layout: '#' comment lines, a header row of letters, then one
+        row per letter (its letter, then n integers): the entry of row r, column c is
+        s(s1 letter r, s2 letter c).  A letter is one character or 0xHH (a byte value).
+        Text with a newline is parsed as it is, anything else is a path.  other=None and
+        a '*' among the letters: '*' is the wildcard, as in NCBI's files."""
+        text = path_or_str
+        if isinstance(text, bytes):
+            text = text.decode("ascii")
+        if "\n" not in text:
+            with open(text) as f:
+                text = f.read()
+        letters, rows = None, {}
+        for line in text.splitlines():
+            tok = line.split()
+            if not tok or tok[0].startswith("#"):
+                continue
+            if letters is None:
+                letters = [_letter_byte(t) for t in tok]
+                continue
+            r = _letter_byte(tok[0])
+            if r not in letters or r in rows or len(tok) != len(letters) + 1:
+                raise ValueError(f"matrix row {line!r}: a letter of the header and {len(letters)} numbers expected")
+            try:
+                rows[r] = [int(t) for t in tok[1:]]
+            except ValueError:
+                raise ValueError(f"matrix row {line!r}: integers expected") from None
+        if letters is None or len(rows) != len(letters):
+            raise ValueError("matrix text: a header row and one row per letter expected")
+        if other is None and ord("*") in letters:
+            other = "*"
+        return cls(letters, np.array([rows[b] for b in letters], np.int64), other)
+
+
+def score_batch_matrix(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, waves: int = 0, device: int = -1,
+                       return_stats: bool = False):
+    """score_batch_affine with substitution by matrix (nw_score_batch_matrix): s(s1 letter,
+    s2 letter) from `mat`, a run of L ups or of L lefts costs gap_open + L * gap."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    mat.check(s1, s2)
+    n = len(pairs)
+    scores = np.zeros(max(n, 1), np.int32)
+    stats = NwBatchStats()
+    p = params((1, 0, int(gap)), waves, device)
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_score_batch_matrix(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
+                                     off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
+                                     int(gap_open), scores.ctypes.data_as(_i32p), ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_score_batch_matrix")
+    return (scores[:n], stats) if return_stats else scores[:n]
+
+
+def align_batch_matrix(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, mem_bytes: int = 0, waves: int = 0,
+                       device: int = -1):
+    """align_batch_affine with substitution by matrix (nw_align_batch_matrix): (scores, [ops
+    of pair 0, ..], NwBatchStats)."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    mat.check(s1, s2)
+    n = len(pairs)
+    ops_off = off1 + off2
+    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
+    scores = np.zeros(max(n, 1), np.int32)
+    n_ops = np.zeros(max(n, 1), np.int64)
+    stats = NwBatchStats()
+    p = params((1, 0, int(gap)), waves, device)
+    o = NwBatchOpts(int(mem_bytes))
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_align_batch_matrix(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
+                                     off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
+                                     int(gap_open), ctypes.byref(o), scores.ctypes.data_as(_i32p),
+                                     ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                     ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_align_batch_matrix")
+    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
+    return scores[:n], out, stats
+
+
+def ops_score_matrix(s1, s2, ops, mat: SubMatrix, gap: int = -1, gap_open: int = 0, begin=(0, 0)) -> int:
+    """Score of an alignment's ops under a matrix and affine gap cost (nw_ops_score_matrix)."""
+    a, b = _seq(s1), _seq(s2)
+    mat.check(a, b)
+    o = np.ascontiguousarray(np.asarray(ops, dtype=np.uint8))
+    p = params((1, 0, int(gap)))
+    sc = ctypes.c_int64()
+    st = lib().nw_ops_score_matrix(a.ctypes.data_as(_i8p), a.size, b.ctypes.data_as(_i8p), b.size, int(begin[0]),
+                                   int(begin[1]), o.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), o.size,
+                                   ctypes.byref(p), ctypes.byref(mat.c), int(gap_open), ctypes.byref(sc))
+    if st != NW_OK:
+        raise NwError(st, "nw_ops_score_matrix")
     return int(sc.value)
 
 
@@ -1112,13 +1308,14 @@ class Context:
         return int(sc.item()), (gran & 0xFFFFFFFF).to(torch.int32)
 
     def score_batch(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, scheme=(1, 0, -1), stream=None,
-                    waves: int = 0, flags: int = 0, gap_open=None):
+                    waves: int = 0, flags: int = 0, gap_open=None, mat=None):
         """Scores of a batch on device tensors (nw_score_batch_async): d_s1cat / d_s2cat
         int8/uint8 CUDA tensors (the concatenations), d_off1 / d_off2 int64 CUDA tensors of
         npairs + 1 offsets, max_n2 >= every pair's n2.  Returns an int32 CUDA tensor of
         npairs scores, ordered on `stream` (default: torch's current stream); nothing is
         synchronised.  Pairs are claimed in index order: submit them longest first.
-        gap_open (an int): affine gap cost, see score_batch_affine (Context.score_batch_affine)."""
+        gap_open (an int): affine gap cost, see score_batch_affine (Context.score_batch_affine).
+        mat (a SubMatrix): substitution by matrix, see Context.score_batch_matrix."""
         import torch
         npairs = int(d_off1.numel()) - 1
         assert d_off1.dtype == torch.int64 and d_off2.dtype == torch.int64 and int(d_off2.numel()) == npairs + 1
@@ -1133,7 +1330,10 @@ class Context:
                 ctypes.c_void_p(d_s2cat.data_ptr() if t2 else 0), ctypes.c_void_p(d_off2.data_ptr()), npairs, t1, t2,
                 int(max_n2), ctypes.byref(p))
         tail = (ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(stream.cuda_stream))
-        if gap_open is None:
+        if mat is not None:
+            st, what = lib().nw_score_batch_matrix_async(*head, ctypes.byref(mat.c), int(gap_open or 0), *tail), \
+                "nw_score_batch_matrix_async"
+        elif gap_open is None:
             st, what = lib().nw_score_batch_async(*head, *tail), "nw_score_batch_async"
         else:
             st, what = lib().nw_score_batch_affine_async(*head, int(gap_open), *tail), "nw_score_batch_affine_async"
@@ -1147,6 +1347,16 @@ class Context:
         or of L lefts costs gap_open + L * scheme[2]."""
         return self.score_batch(d_s1cat, d_off1, d_s2cat, d_off2, max_n2, scheme, stream, waves, flags,
                                 gap_open=int(gap_open))
+
+    def score_batch_matrix(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, mat: SubMatrix, gap: int = -1,
+                           gap_open: int = 0, stream=None, waves: int = 0):
+        """score_batch_affine with substitution by matrix (nw_score_batch_matrix_async).  The
+        sequences stay on the device and are not looked at: the matrix must name the
+        letter unlisted bytes map to (SubMatrix(.., other=))."""
+        if mat.other is None and not mat.listed.all():
+            raise ValueError("Context.score_batch_matrix needs a matrix with other= (it cannot check the sequences)")
+        return self.score_batch(d_s1cat, d_off1, d_s2cat, d_off2, max_n2, (1, 0, int(gap)), stream, waves, 0,
+                                gap_open=int(gap_open), mat=mat)
 
     def traceback_block(self, d_s1, d_s2_block, table, row0: int, scheme=(1, 0, -1), stream=None, band: int = 0,
                         max_windows: int = 0, no_aim: bool = False):

@@ -514,6 +514,51 @@ int nw_align_batch_affine(const int8_t *s1cat, const int64_t *off1, const int8_t
                           int32_t *scores, uint8_t *ops, const int64_t *ops_off, int64_t *n_ops,
                           nw_batch_stats *stats);
 
+/* Batched global alignment with a substitution matrix ---------------------------
+ * The affine entries above with s(s1[j-1], s2[i-1]) = score[index[s1[j-1]]][index[s2[i-
+ * 1]]] in the place of match / mismatch: BLOSUM / PAM for proteins, transition /
+ * transversion and IUPAC matrices for nucleotides.  At most NW_SUBMAT_MAX letters;
+ * EVERY byte value maps to a letter -- a caller who wants "unknown" points those bytes
+ * at its own wildcard letter (X, N, *); there is no separate unknown-character path and
+ * the sequences are never scanned on the host.  The matrix may be asymmetric: the first
+ * index is always the s1 (column) letter.  Entries at or beyond n are ignored.
+ * nw_params.gap is the extension and gap_open the opening, as above (gap_open = 0: the
+ * linear cost with a matrix); match and mismatch are not used but must be valid.  The
+ * recurrence, the boundaries, the three-state walk and its tie-breaks are word for word
+ * those of the affine entries, and so are the CSR layout, options, statistics, slot
+ * sizes, chunking, nw_batch_affine_dir_bytes, the empty-side pairs and the INT32_MIN of
+ * a pair longer than max_n2 in the _async form (kernels: csrc/nw_batch_matrix.hip; the
+ * matrix travels in the kernel arguments, a worker keeps a profile of its four columns
+ * in 8 KiB of LDS).  The refusals and their order are the affine entries'; also
+ * NW_ERR_ARG, after the parameter checks: m == NULL, n outside 1 .. NW_SUBMAT_MAX, a
+ * reserved word != 0, an index entry >= n; and a pair beyond
+ *   3*|gap_open| + (M + |gap|) * (n1 + n2 + 2) < 2^28,  M = max(|gap|, max |score[x][y]|
+ *   over x, y < n)
+ * -- the affine range with the matrix's largest entry in the place of match / mismatch.
+ * Exact for every int8 matrix and every gap that bound admits. */
+enum { NW_SUBMAT_MAX = 32 };
+typedef struct nw_submat {
+    int32_t n;              /* letters, 1..NW_SUBMAT_MAX */
+    int32_t reserved[3];    /* must be 0 */
+    uint8_t index[256];     /* byte (as unsigned) -> letter 0..n-1; every entry < n */
+    int8_t  score[NW_SUBMAT_MAX * NW_SUBMAT_MAX];
+                            /* score[x * NW_SUBMAT_MAX + y] = s(s1 letter x, s2 letter y) */
+} nw_submat;
+
+int nw_score_batch_matrix_async(nw_ctx *ctx, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                                const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2,
+                                int64_t max_n2, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                                int32_t *d_scores, void *stream);
+
+int nw_score_batch_matrix(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                          int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t *scores,
+                          nw_batch_stats *stats);
+
+int nw_align_batch_matrix(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                          int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                          const nw_batch_opts *o, int32_t *scores, uint8_t *ops, const int64_t *ops_off,
+                          int64_t *n_ops, nw_batch_stats *stats);
+
 /* Launch-only variant for timing loops: no synchronisation, no readback. */
 int nw_fill_device_async(nw_ctx *ctx, const int8_t *d_s1, int64_t n1,
                          const int8_t *d_s2, int64_t n2, const nw_params *p,
@@ -766,6 +811,12 @@ int nw_ops_score(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int
 int nw_ops_score_affine(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t begin_i,
                         int64_t begin_j, const uint8_t *ops, int64_t n_ops, const nw_params *p, int32_t gap_open,
                         int64_t *score);
+/* nw_ops_score_matrix: nw_ops_score_affine with score[index[s1[j]]][index[s2[i]]] per op 0;
+ *   also NW_ERR_ARG for m == NULL, n outside 1 .. NW_SUBMAT_MAX, a reserved word != 0, an
+ *   index entry >= n. */
+int nw_ops_score_matrix(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t begin_i,
+                        int64_t begin_j, const uint8_t *ops, int64_t n_ops, const nw_params *p, const nw_submat *m,
+                        int32_t gap_open, int64_t *score);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,13 @@ library's one-pair path, unchanged by the batch; its scores must equal the batch
                     of the two; no host loop (the one-pair entries have no affine form).
                     Writes profiles/batch_affine_time.json; profiles/batch_time.json stays.
 
+  --matrix N        the matrix entries (nw_score_batch_matrix, nw_align_batch_matrix) on pairs over
+                    a seeded random N-letter alphabet under a seeded symmetric int8 matrix with
+                    entries in -4..11 (BLOSUM62's span), gap -1 and --gap-open (default -11); in
+                    the same process the affine entries on 4-letter pairs of the same sizes (the
+                    yardstick: code the matrix does not touch) and the two ratios.  Writes
+                    profiles/batch_matrix_time.json.
+
 The score kernel's yardstick is the checkpoint sweep's pace on one huge table
 (profiles/ckpt_time.json: 262144^2 in 20.62 ms); `fraction_of_sweep_pace` states it.
 """
@@ -42,10 +49,14 @@ ap.add_argument("--shape", default="all")
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--loop-reps", type=int, default=5)
 ap.add_argument("--gap-open", type=int, default=None)
+ap.add_argument("--matrix", type=int, default=None, nargs="?", const=20)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
+if args.matrix is not None and args.gap_open is None:
+    args.gap_open = -11
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "batch_time.json" if args.gap_open is None else "batch_affine_time.json")
+    args.out = os.path.join(ROOT, "profiles", "batch_matrix_time.json" if args.matrix is not None else
+                            "batch_time.json" if args.gap_open is None else "batch_affine_time.json")
 scheme = (1, 0, -1)
 med = statistics.median
 
@@ -56,14 +67,27 @@ def wall(f):
     return (time.perf_counter() - t0) * 1e3, r
 
 
-def make_pairs(name):
+def make_pairs(name, letters=None):
+    """The shape's pairs over the bytes 1..4, or over `letters` (same seed, same sizes)."""
     npairs, lo, hi = SHAPES[name]
     rng = np.random.default_rng(npairs)
     if name == "mixed":
         lens = rng.integers(lo, hi + 1, (npairs, 2))
     else:
         lens = np.tile([lo, hi], (npairs, 1))
-    return [(rng.integers(1, 5, int(a)).astype(np.int8), rng.integers(1, 5, int(b)).astype(np.int8)) for a, b in lens]
+    if letters is None:
+        letters = np.arange(1, 5, dtype=np.int8)
+    k = len(letters)
+    return [(letters[rng.integers(0, k, int(a))], letters[rng.integers(0, k, int(b))]) for a, b in lens]
+
+
+def make_matrix(n):
+    """A seeded random n-letter alphabet and a seeded symmetric matrix with entries in -4..11."""
+    rng = np.random.default_rng(62 + n)
+    letters = np.sort(rng.choice(np.arange(1, 128), n, replace=False)).astype(np.int8)
+    sc = rng.integers(-4, 12, (n, n))
+    sc = np.triu(sc) + np.triu(sc, 1).T
+    return letters, nwhip.SubMatrix(letters.tolist(), sc, other=int(letters[0]))
 
 
 def time_entries(pairs, cells, score_f, align_f):
@@ -101,6 +125,29 @@ def run_affine(name):
     e["score_affine_over_linear"] = round(s["fill_ms"] / ls["fill_ms"], 2)
     e["align_fill_affine_over_linear"] = round(a["fill_ms"] / la["fill_ms"], 2)
     e["align_fill_walk_affine_over_linear"] = round(a["fill_walk_ms"] / la["fill_walk_ms"], 2)
+    print(json.dumps(e), flush=True)
+    return e
+
+
+def run_matrix(name):
+    go, ge = args.gap_open, -1
+    letters, mat = make_matrix(args.matrix)
+    pairs4 = make_pairs(name)
+    pairs = make_pairs(name, letters)
+    cells = sum(a.size * b.size for a, b in pairs)
+    assert cells == sum(a.size * b.size for a, b in pairs4)
+    e = {"shape": name, "pairs": len(pairs), "cells": int(cells), "gap_open": go, "gap": ge, "letters": args.matrix,
+         "matrix_entries": [int(mat.scores.min()), int(mat.scores.max())],
+         "lengths": "uniform %d..%d" % SHAPES[name][1:] if name == "mixed" else "%d x %d" % SHAPES[name][1:]}
+    fs, fa, _ = time_entries(pairs4, cells, lambda p, **kw: nwhip.score_batch_affine(p, (1, 0, ge), go, **kw),
+                             lambda p: nwhip.align_batch_affine(p, (1, 0, ge), go))
+    s, a, _ = time_entries(pairs, cells, lambda p, **kw: nwhip.score_batch_matrix(p, mat, ge, go, **kw),
+                           lambda p: nwhip.align_batch_matrix(p, mat, ge, go))
+    e["score_batch_affine"], e["align_batch_affine"] = fs, fa
+    e["score_batch_matrix"], e["align_batch_matrix"] = s, a
+    e["score_matrix_over_affine"] = round(s["fill_ms"] / fs["fill_ms"], 2)
+    e["align_fill_matrix_over_affine"] = round(a["fill_ms"] / fa["fill_ms"], 2)
+    e["align_fill_walk_matrix_over_affine"] = round(a["fill_walk_ms"] / fa["fill_walk_ms"], 2)
     print(json.dumps(e), flush=True)
     return e
 
@@ -149,7 +196,8 @@ if os.path.exists(args.out):
 rec.update({"device": torch.cuda.get_device_name(0), "library": nwhip.version(), "scheme": list(scheme),
             "reps": args.reps, "sweep_yardstick_gcups": round(SWEEP_GCUPS, 1)})
 for name in (list(SHAPES) if args.shape == "all" else [args.shape]):
-    rec["shapes"][name] = run(name) if args.gap_open is None else run_affine(name)
+    rec["shapes"][name] = (run_matrix(name) if args.matrix is not None else
+                           run(name) if args.gap_open is None else run_affine(name))
 os.makedirs(os.path.dirname(args.out), exist_ok=True)
 with open(args.out, "w") as f:
     json.dump(rec, f, indent=1)
