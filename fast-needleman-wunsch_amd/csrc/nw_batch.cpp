@@ -8,7 +8,11 @@
 // entries (nw_score_batch_matrix_async, nw_score_batch_matrix, nw_align_batch_matrix;
 // kernels in nw_batch_matrix.hip) are the affine ones with the substitution read from an
 // nw_submat: the Cost carries the matrix, batch_prepare maps the rows through its index
-// instead of running the charmap, and batch_run launches the matrix sweep.
+// instead of running the charmap, and batch_run launches the matrix sweep.  The local
+// entries (nw_score_batch_local_async, nw_score_batch_local, nw_align_batch_local; kernels
+// in nw_batch_local.hip) are the matrix ones in mode NW_MODE_SW: a pair's result is an
+// nw_local_hit where the others have an int32 score, the matrix goes into the arguments
+// as it is, and the walk starts at the hit the sweep left on the device.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -30,6 +34,8 @@ struct Cost {
     bool matrix = false;  // substitution by *mat (affine is then true): matrix_cost()
     const nw_submat *mat = nullptr;
     int64_t mat_abs = 0;  // max |score[x][y]| over x, y < n
+    bool local = false;   // Smith-Waterman (matrix is then true): a result is an nw_local_hit
+    size_t out_bytes() const { return local ? sizeof(nw_local_hit) : sizeof(int32_t); }
     int64_t col_words(int64_t max_n2) const { return nw::batch_col_words(max_n2) * (affine ? 2 : 1); }
     int64_t dir_bytes(int64_t n1, int64_t n2) const {
         return affine ? nw_batch_affine_dir_bytes(n1, n2) : nw_batch_dir_bytes(n1, n2);
@@ -54,7 +60,10 @@ bool valid_submat(const nw_submat *m) {
 }
 
 Cost matrix_cost(const nw_submat *m, int32_t gap_open) {
-    Cost c{true, gap_open, true, m};
+    Cost c;
+    c.affine = c.matrix = true;
+    c.open = gap_open;
+    c.mat = m;
     if (valid_submat(m))  // (an invalid one is refused by params_check before the range is looked at)
         for (int x = 0; x < m->n; ++x)
             for (int y = 0; y < m->n; ++y)
@@ -62,11 +71,26 @@ Cost matrix_cost(const nw_submat *m, int32_t gap_open) {
     return c;
 }
 
+Cost local_cost(const nw_submat *m, int32_t gap_open) {
+    Cost c = matrix_cost(m, gap_open);
+    c.local = true;
+    return c;
+}
+
+// the hit of a pair without cells, or whose best is 0: nothing aligned
+nw_local_hit empty_hit(int32_t begin) {
+    nw_local_hit h;
+    std::memset(&h, 0, sizeof h);
+    h.begin_i = h.begin_j = begin;
+    return h;
+}
+
 // The matrix into the launch's arguments.  The cells hold the w form, which adds s - 2
 // gap per diagonal: those bytes when every one of them fits int8 (the kernel then adds
 // nothing), else s itself and the kernel adds -2 gap per cell (wide).  Entries beyond n
 // are 0 whatever the caller left there.
-void submat_args(const nw_submat *m, int32_t gap, nw::BatchMatrixArgs *ma) {
+void submat_args(const nw_submat *m, int32_t gap, bool local, nw::BatchMatrixArgs *ma) {
+    if (local) gap = 0;  // (the local cells are not in the w form: the bytes are s itself, and fit)
     bool fits = true;
     for (int x = 0; x < m->n && fits; ++x)
         for (int y = 0; y < m->n; ++y) {
@@ -88,7 +112,7 @@ void submat_args(const nw_submat *m, int32_t gap, nw::BatchMatrixArgs *ma) {
 // what every batch entry refuses in its parameters, judged without a device
 // (NW_KERNEL_PANELS, which is NW_ERR_UNSUPPORTED, comes after every NW_ERR_ARG)
 int params_check(const nw_params *p, int64_t npairs, const Cost &cost) {
-    if (!valid_params(p) || p->mode != NW_MODE_NW) return NW_ERR_ARG;
+    if (!valid_params(p) || p->mode != (cost.local ? NW_MODE_SW : NW_MODE_NW)) return NW_ERR_ARG;
     if ((p->flags & ~NW_FLAG_NO_PROFILE) != 0) return NW_ERR_ARG;
     // with a positive gap_open the walk would open a new gap at every step, and the ops
     // would no longer determine the score
@@ -105,7 +129,7 @@ struct Batch {
 };
 
 int batch_check(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2, int64_t npairs,
-                const nw_params *p, const Cost &cost, const int32_t *scores, Batch *b) {
+                const nw_params *p, const Cost &cost, const void *scores, Batch *b) {
     int st = params_check(p, npairs, cost);
     if (st != NW_OK) return st;
     if (npairs == 0) return NW_OK;
@@ -155,7 +179,7 @@ int batch_prepare(nw_ctx *c, const int8_t *d_s1, const int64_t *d_off1, int64_t 
         if (nw::launch_batch_matrix_rows((const uint8_t *)d_s2, total2, cost.mat->index, (uint8_t *)c->rowpack,
                                          stream) != hipSuccess)
             return NW_ERR_HIP;
-        submat_args(cost.mat, p->gap, ma);
+        submat_args(cost.mat, p->gap, cost.local, ma);
     } else {
         if (nw::launch_charmap((const uint8_t *)d_s1, total1, c->meta, stream) != hipSuccess) return NW_ERR_HIP;
         if (nw::launch_batch_rows((const uint8_t *)d_s2, total2, perm_ok ? 1 : 0, c->meta, (uint8_t *)c->rowpack,
@@ -183,14 +207,23 @@ int batch_prepare(nw_ctx *c, const int8_t *d_s1, const int64_t *d_off1, int64_t 
     return NW_OK;
 }
 
-// one launch of the batch kernel over a->npairs tickets
+// one launch of the batch kernel over a->npairs tickets (local: ma.a.b.scores holds the
+// hits)
 int batch_run(nw_ctx *c, const nw::BatchMatrixArgs &ma, const Cost &cost, bool dirs, int grid, void *stream) {
     if (nw::launch_ctrl_reset(c->ctrl, stream) != hipSuccess) return NW_ERR_HIP;
     const nw::BatchAffineArgs &aa = ma.a;
     const int g = std::min(grid, std::max(aa.b.npairs, 1));
-    const int e = cost.matrix   ? nw::launch_batch_matrix(ma, dirs, g, stream)
-                  : cost.affine ? nw::launch_batch_affine(aa, dirs, g, stream)
-                                : nw::launch_batch(aa.b, dirs, g, stream);
+    int e;
+    if (cost.local) {
+        nw::BatchLocalArgs la;
+        la.m = ma;
+        la.hits = ma.a.b.scores;
+        la.m.a.b.scores = nullptr;
+        e = nw::launch_batch_local(la, dirs, g, stream);
+    } else
+        e = cost.matrix ? nw::launch_batch_matrix(ma, dirs, g, stream)
+            : cost.affine ? nw::launch_batch_affine(aa, dirs, g, stream)
+                          : nw::launch_batch(aa.b, dirs, g, stream);
     if (e != hipSuccess) return NW_ERR_HIP;
     c->last_waves = grid;
     c->last_kernel = NW_KERNEL_STRIPS;
@@ -204,7 +237,7 @@ struct BatchDev {
     int32_t *order = nullptr, *scores = nullptr;
     int64_t bytes = 0;
     int upload(DevBufs &bufs, const int8_t *s1cat, const int64_t *h_off1, const int8_t *s2cat, const int64_t *h_off2,
-               int64_t npairs, const Batch &b) {
+               int64_t npairs, const Batch &b, const Cost &cost) {
         int st;
         const size_t ob = (size_t)(npairs + 1) * 8, cnt = b.order.size();
         if ((st = bufs.alloc((void **)&s1, (size_t)b.total1)) != NW_OK) return st;
@@ -212,7 +245,7 @@ struct BatchDev {
         if ((st = bufs.alloc((void **)&off1, ob)) != NW_OK) return st;
         if ((st = bufs.alloc((void **)&off2, ob)) != NW_OK) return st;
         if ((st = bufs.alloc((void **)&order, cnt * 4)) != NW_OK) return st;
-        if ((st = bufs.alloc((void **)&scores, (size_t)npairs * 4)) != NW_OK) return st;
+        if ((st = bufs.alloc((void **)&scores, (size_t)npairs * cost.out_bytes())) != NW_OK) return st;
         if (b.total1 > 0) NW_HIP_TRY(hipMemcpy(s1, s1cat, (size_t)b.total1, hipMemcpyHostToDevice));
         if (b.total2 > 0) NW_HIP_TRY(hipMemcpy(s2, s2cat, (size_t)b.total2, hipMemcpyHostToDevice));
         NW_HIP_TRY(hipMemcpy(off1, h_off1, ob, hipMemcpyHostToDevice));
@@ -220,8 +253,9 @@ struct BatchDev {
         NW_HIP_TRY(hipMemcpy(order, b.order.data(), cnt * 4, hipMemcpyHostToDevice));
         return NW_OK;
     }
-    static int64_t need(int64_t npairs, const Batch &b) {
-        return b.total1 + b.total2 + 2 * (npairs + 1) * 8 + (int64_t)b.order.size() * 4 + npairs * 4;
+    static int64_t need(int64_t npairs, const Batch &b, const Cost &cost) {
+        return b.total1 + b.total2 + 2 * (npairs + 1) * 8 + (int64_t)b.order.size() * 4 +
+               npairs * (int64_t)cost.out_bytes();
     }
 };
 
@@ -238,7 +272,7 @@ int64_t workers(const nw_ctx *c, const nw_params *p, int64_t tickets) {
 
 int score_batch_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
                       const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2, int64_t max_n2,
-                      const nw_params *p, const Cost &cost, int32_t *d_scores, void *stream) {
+                      const nw_params *p, const Cost &cost, void *d_scores, void *stream) {
     int st = params_check(p, npairs, cost);
     if (st != NW_OK) return st;
     if (total1 < 0 || total2 < 0 || max_n2 < 0 || max_n2 >= INT32_MAX || max_n2 > total2) return NW_ERR_ARG;
@@ -254,19 +288,22 @@ int score_batch_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, c
                             &grid)) != NW_OK)
         return st;
     ma.a.b.npairs = (int32_t)npairs;  // (tickets in index order: the lengths are on the device)
-    ma.a.b.scores = d_scores;
+    ma.a.b.scores = (int32_t *)d_scores;
     return batch_run(c, ma, cost, false, grid, stream);
 }
 
 int score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2, int64_t npairs,
-                const nw_params *p, const Cost &cost, int32_t *scores, nw_batch_stats *stats) {
+                const nw_params *p, const Cost &cost, void *out, nw_batch_stats *stats) {
+    int32_t *scores = (int32_t *)out;          // (global entries)
+    nw_local_hit *hits = (nw_local_hit *)out;  // (local entries)
     nw_params def;
     if (!p) {
         nw_params_default(&def);
+        if (cost.local) def.mode = NW_MODE_SW;
         p = &def;
     }
     Batch b;
-    int st = batch_check(s1cat, off1, s2cat, off2, npairs, p, cost, scores, &b);
+    int st = batch_check(s1cat, off1, s2cat, off2, npairs, p, cost, out, &b);
     if (st != NW_OK) return st;
     if (p->kernel == NW_KERNEL_PANELS) return NW_ERR_UNSUPPORTED;
     int dev;
@@ -280,7 +317,11 @@ int score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
     batch_order(off1, off2, npairs, &b);
     for (int64_t i = 0; i < npairs; ++i) {  // no cells: the corner of the boundary
         const int64_t n1 = off1[i + 1] - off1[i], n2 = off2[i + 1] - off2[i];
-        if (n1 == 0 || n2 == 0) scores[i] = cost.empty_score(p, std::max(n1, n2));
+        if (n1 != 0 && n2 != 0) continue;
+        if (cost.local)
+            hits[i] = empty_hit(-1);
+        else
+            scores[i] = cost.empty_score(p, std::max(n1, n2));
     }
     const int64_t cnt = (int64_t)b.order.size();
     if (cnt == 0) return NW_OK;
@@ -291,7 +332,7 @@ int score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
     NW_HIP_TRY(hipSetDevice(dev));
     DevBufs bufs;
     BatchDev d;
-    if ((st = d.upload(bufs, s1cat, off1, s2cat, off2, npairs, b)) != NW_OK) return st;
+    if ((st = d.upload(bufs, s1cat, off1, s2cat, off2, npairs, b, cost)) != NW_OK) return st;
     nw::BatchMatrixArgs ma;
     int grid = 0;
     if ((st = batch_prepare(c, d.s1, d.off1, b.total1, d.s2, d.off2, b.total2, b.max_n2, p, cost, cnt, nullptr, &ma,
@@ -303,29 +344,33 @@ int score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
     NW_HIP_TRY(hipEventRecord(c->ev0, nullptr));
     if ((st = batch_run(c, ma, cost, false, grid, nullptr)) != NW_OK) return st;
     NW_HIP_TRY(hipEventRecord(c->ev1, nullptr));
-    std::vector<int32_t> got((size_t)npairs);
-    NW_HIP_TRY(hipMemcpy(got.data(), d.scores, (size_t)npairs * 4, hipMemcpyDeviceToHost));
-    for (int32_t i : b.order) scores[i] = got[(size_t)i];
+    const size_t ob = cost.out_bytes();
+    std::vector<uint8_t> got((size_t)npairs * ob);
+    NW_HIP_TRY(hipMemcpy(got.data(), d.scores, got.size(), hipMemcpyDeviceToHost));
+    for (int32_t i : b.order) std::memcpy((uint8_t *)out + (size_t)i * ob, got.data() + (size_t)i * ob, ob);
     float ms = 0.f;
     NW_HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     bs.chunks = 1;
     bs.waves = grid;
     bs.fill_ms = ms;
-    bs.peak_bytes = BatchDev::need(npairs, b) + workspace_need(b, grid, cost);
+    bs.peak_bytes = BatchDev::need(npairs, b, cost) + workspace_need(b, grid, cost);
     if (stats) *stats = bs;
     return NW_OK;
 }
 
 int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2, int64_t npairs,
-                const nw_params *p, const Cost &cost, const nw_batch_opts *o, int32_t *scores, uint8_t *ops,
+                const nw_params *p, const Cost &cost, const nw_batch_opts *o, void *out, uint8_t *ops,
                 const int64_t *ops_off, int64_t *n_ops, nw_batch_stats *stats) {
+    int32_t *scores = (int32_t *)out;          // (global entries)
+    nw_local_hit *hits = (nw_local_hit *)out;  // (local entries)
     nw_params def;
     if (!p) {
         nw_params_default(&def);
+        if (cost.local) def.mode = NW_MODE_SW;
         p = &def;
     }
     Batch b;
-    int st = batch_check(s1cat, off1, s2cat, off2, npairs, p, cost, scores, &b);
+    int st = batch_check(s1cat, off1, s2cat, off2, npairs, p, cost, out, &b);
     if (st != NW_OK) return st;
     int64_t mem = 0;
     if (o) {
@@ -355,6 +400,11 @@ int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
     for (int64_t i = 0; i < npairs; ++i) {  // no cells: all ups or all lefts
         const int64_t n1 = off1[i + 1] - off1[i], n2 = off2[i + 1] - off2[i];
         if (n1 != 0 && n2 != 0) continue;
+        if (cost.local) {  // nothing aligned
+            hits[i] = empty_hit(0);
+            n_ops[i] = 0;
+            continue;
+        }
         const int64_t n = std::max(n1, n2);
         scores[i] = cost.empty_score(p, n);
         n_ops[i] = n;
@@ -375,7 +425,7 @@ int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
     // The chunks: consecutive runs of the longest-first order whose direction blocks
     // and ops slots fit what the budget leaves after everything else the call holds.
     const int64_t waves = workers(c, p, cnt);
-    const int64_t fixed = BatchDev::need(npairs, b) + workspace_need(b, waves, cost) + cnt * 3 * 8;
+    const int64_t fixed = BatchDev::need(npairs, b, cost) + workspace_need(b, waves, cost) + cnt * 3 * 8;
     std::vector<int64_t> dir_off((size_t)cnt), loc_off((size_t)cnt);
     std::vector<int64_t> chunk_first;  // ticket where each chunk starts (+ the end)
     int64_t cur_dir = 0, cur_ops = 0, max_dir = 0, max_ops = 0;
@@ -404,7 +454,7 @@ int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
     DevBufs bufs;
     BatchDev d;
     Events ef, ew;
-    if ((st = d.upload(bufs, s1cat, off1, s2cat, off2, npairs, b)) != NW_OK) return st;
+    if ((st = d.upload(bufs, s1cat, off1, s2cat, off2, npairs, b, cost)) != NW_OK) return st;
     uint8_t *d_dirs = nullptr, *d_ops = nullptr;
     int64_t *d_dir_off = nullptr, *d_loc_off = nullptr, *d_nops = nullptr;
     if ((st = bufs.alloc((void **)&d_dirs, (size_t)max_dir)) != NW_OK) return st;
@@ -444,8 +494,15 @@ int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
         NW_HIP_TRY(hipEventRecord(ef.a, nullptr));
         if ((st = batch_run(c, ma, cost, true, grid, nullptr)) != NW_OK) return st;
         NW_HIP_TRY(hipEventRecord(ef.b, nullptr));
-        if ((cost.affine ? nw::launch_batch_affine_walk(w, nullptr) : nw::launch_batch_walk(w, nullptr)) != hipSuccess)
-            return NW_ERR_HIP;
+        int e;
+        if (cost.local) {  // the walk reads its start from the hit on the device and adds the begin cell
+            nw::BatchLocalWalkArgs lw;
+            lw.w = w;
+            lw.hits = d.scores;
+            e = nw::launch_batch_local_walk(lw, nullptr);
+        } else
+            e = cost.affine ? nw::launch_batch_affine_walk(w, nullptr) : nw::launch_batch_walk(w, nullptr);
+        if (e != hipSuccess) return NW_ERR_HIP;
         NW_HIP_TRY(hipEventRecord(ew.b, nullptr));
         // the chunk's ops: one copy (which also orders the next chunk's launches after
         // this chunk's walk), then each pair's slot into the caller's
@@ -464,13 +521,14 @@ int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
         NW_HIP_TRY(hipEventElapsedTime(&ms, ef.b, ew.b));
         bs.walk_ms += ms;
     }
-    std::vector<int32_t> got((size_t)npairs);
+    const size_t ob = cost.out_bytes();
+    std::vector<uint8_t> got((size_t)npairs * ob);
     std::vector<int64_t> gotn((size_t)cnt);
-    NW_HIP_TRY(hipMemcpy(got.data(), d.scores, (size_t)npairs * 4, hipMemcpyDeviceToHost));
+    NW_HIP_TRY(hipMemcpy(got.data(), d.scores, got.size(), hipMemcpyDeviceToHost));
     NW_HIP_TRY(hipMemcpy(gotn.data(), d_nops, (size_t)cnt * 8, hipMemcpyDeviceToHost));
     for (int64_t t = 0; t < cnt; ++t) {
         const int32_t i = b.order[(size_t)t];
-        scores[i] = got[(size_t)i];
+        std::memcpy((uint8_t *)out + (size_t)i * ob, got.data() + (size_t)i * ob, ob);
         n_ops[i] = gotn[(size_t)t];
     }
     if (stats) *stats = bs;
@@ -552,6 +610,28 @@ int nw_align_batch_matrix(const int8_t *s1cat, const int64_t *off1, const int8_t
                           int64_t *n_ops, nw_batch_stats *stats) {
     return align_batch(s1cat, off1, s2cat, off2, npairs, p, matrix_cost(m, gap_open), o, scores, ops, ops_off,
                        n_ops, stats);
+}
+
+int nw_score_batch_local_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                               const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2,
+                               int64_t max_n2, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                               nw_local_hit *d_hits, void *stream) {
+    return score_batch_async(c, d_s1cat, d_off1, d_s2cat, d_off2, npairs, total1, total2, max_n2, p,
+                             local_cost(m, gap_open), d_hits, stream);
+}
+
+int nw_score_batch_local(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                         int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                         nw_local_hit *hits, nw_batch_stats *stats) {
+    return score_batch(s1cat, off1, s2cat, off2, npairs, p, local_cost(m, gap_open), hits, stats);
+}
+
+int nw_align_batch_local(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                         int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                         const nw_batch_opts *o, nw_local_hit *hits, uint8_t *ops, const int64_t *ops_off,
+                         int64_t *n_ops, nw_batch_stats *stats) {
+    return align_batch(s1cat, off1, s2cat, off2, npairs, p, local_cost(m, gap_open), o, hits, ops, ops_off, n_ops,
+                       stats);
 }
 
 }  // extern "C"

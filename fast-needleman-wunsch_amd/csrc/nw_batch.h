@@ -79,6 +79,22 @@ struct BatchMatrixArgs {
     uint8_t index[256];  // byte -> letter < n
 };
 
+// The local kernels (nw_batch_local.hip): the matrix launch's arguments (m.wide 0 and
+// m.score the matrix's own bytes: the cells are not in the w form; m.a.b.scores unused)
+// and the hits, kBatchLocalHitWords int32 per pair in nw_local_hit's layout.
+constexpr int kBatchLocalHitWords = 8;
+struct BatchLocalArgs {
+    BatchMatrixArgs m;
+    int32_t *hits;  // [pair][8]: score, end_i, end_j, begin_i, begin_j, 0, 0, 0
+};
+
+// The local walk: from the hit's end cell to the first cell with H == 0, which it writes
+// into the hit as the begin cell.
+struct BatchLocalWalkArgs {
+    BatchWalkArgs w;
+    int32_t *hits;
+};
+
 // mapped (perm and at most kMaxPerm distinct column characters) or raw copy of s2cat
 int launch_batch_rows(const uint8_t *d_s2, int64_t total2, int32_t perm, const uint8_t *meta, uint8_t *d_rows,
                       void *stream);
@@ -93,5 +109,9 @@ int launch_batch_affine_walk(const BatchWalkArgs &w, void *stream);
 int launch_batch_matrix_rows(const uint8_t *d_s2, int64_t total2, const uint8_t *index, uint8_t *d_rows,
                              void *stream);
 int launch_batch_matrix(const BatchMatrixArgs &a, bool dirs, int grid, void *stream);
+// local alignment (Smith-Waterman) with the matrix: the sweep writes a hit per pair, the
+// walk starts at the hit's end cell (then the reversal, as above)
+int launch_batch_local(const BatchLocalArgs &a, bool dirs, int grid, void *stream);
+int launch_batch_local_walk(const BatchLocalWalkArgs &w, void *stream);
 
 }  // namespace nw

@@ -7,7 +7,7 @@
 //   --mem BYTES / --block-rows K: align in linear memory (nw_align_ckpt) within BYTES
 //   of device memory / in blocks of K rows (a multiple of 64); the output is the same.
 //   --score-only: no alignment, the score from the table-free sweep (nw_score).
-//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only] [--gap-open G] [--matrix FILE]
+//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only] [--gap-open G] [--matrix FILE] [--local]
 //   LIST: a text file, one pair "A.bdna B.bdna" per line (paths relative to the
 //   list's directory unless absolute); all pairs are aligned in ONE call
 //   (nw_align_batch; --score-only: nw_score_batch).  stdout: "<ms>\n", then one
@@ -22,6 +22,14 @@
 //   c.  A letter is one character or 0xHH (a byte value); a lower-case byte maps like its
 //   upper-case letter; with a '*' among the letters every unlisted byte maps to it,
 //   without one an unlisted byte in a sequence is an error.
+//   --local (with --batch only): local alignment, Smith-Waterman under the same gap cost
+//   (nw_align_batch_local / nw_score_batch_local): the best-scoring pair of substrings
+//   of every pair.  Without --matrix the substitution is --scheme's match / mismatch over
+//   A, C, G, T (either case); every other byte is one more letter that mismatches
+//   everything, itself included.  Per pair one line
+//     "Score: <max H> begin (<i>, <j>) end (<i>, <j>)"     (cells of the table: i counts B)
+//   and, unless --score-only (which prints no begin cell), the two gapped rows of the
+//   aligned segment alone, "A: ..." and "B: ..." ('-' = gap, a non-printing byte as '?').
 // Argument and missing-file errors are nw_driver's (exit 1); a device failure is
 // reported on stderr and exits 2.
 #include <chrono>
@@ -118,11 +126,44 @@ static bool read_matrix(const char *path, nw_submat *m, bool *listed, std::strin
     return true;
 }
 
+// --local without --matrix: match / mismatch over A, C, G, T (either case) and one more
+// letter for every other byte, which mismatches everything, itself included
+static void uniform_dna(const nw_params &p, nw_submat *m, bool *listed) {
+    std::memset(m, 0, sizeof *m);
+    m->n = 5;
+    for (int x = 0; x < 5; ++x)
+        for (int y = 0; y < 5; ++y)
+            m->score[x * NW_SUBMAT_MAX + y] = (int8_t)(x == y && x < 4 ? p.match : p.mismatch);
+    for (int b = 0; b < 256; ++b) {
+        listed[b] = true;
+        m->index[b] = 4;
+    }
+    const char *acgt = "ACGT";
+    for (int k = 0; k < 4; ++k) m->index[(unsigned char)acgt[k]] = m->index[(unsigned char)acgt[k] + 32] = (uint8_t)k;
+}
+
+static std::string row_text(const std::vector<int8_t> &row) {
+    std::string t(row.size(), '?');
+    for (size_t k = 0; k < row.size(); ++k)
+        if (row[k] == 0)
+            t[k] = '-';
+        else if (row[k] > 32 && row[k] < 127)
+            t[k] = (char)row[k];
+    return t;
+}
+
 // --batch LIST: every pair of the list in one call
 static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bool score_only, const int32_t *gap_open,
-                     const char *matrix) {
+                     const char *matrix, bool local) {
     nw_submat mat;
     bool listed[256];
+    if (local && matrix == nullptr) {
+        if (p.match < -128 || p.match > 127 || p.mismatch < -128 || p.mismatch > 127) {
+            std::cout << "error: --local without --matrix needs match and mismatch in -128..127" << std::endl;
+            return 1;
+        }
+        uniform_dna(p, &mat, listed);
+    }
     if (matrix != nullptr) {
         std::string err;
         if (!read_matrix(matrix, &mat, listed, &err)) {
@@ -158,7 +199,7 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
                 std::cout << "ERROR: no such file " << path << std::endl;
                 return 1;
             }
-            if (matrix != nullptr)
+            if (matrix != nullptr || local)
                 for (int64_t x = 0; x < n; ++x)
                     if (!listed[(unsigned char)s[x]]) {
                         std::cout << "ERROR: byte " << (int)(unsigned char)s[x] << " of " << path
@@ -181,7 +222,14 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
     bo.mem_bytes = mem_bytes;
     auto wallStart = std::chrono::system_clock::now();
     int st;
-    if (matrix != nullptr)
+    std::vector<nw_local_hit> hits((size_t)npairs + 1);
+    if (local)
+        st = score_only ? nw_score_batch_local(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
+                                               gap_open ? *gap_open : 0, hits.data(), nullptr)
+                        : nw_align_batch_local(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
+                                               gap_open ? *gap_open : 0, &bo, hits.data(), ops.data(), ops_off.data(),
+                                               n_ops.data(), nullptr);
+    else if (matrix != nullptr)
         st = score_only ? nw_score_batch_matrix(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
                                                 gap_open ? *gap_open : 0, scores.data(), nullptr)
                         : nw_align_batch_matrix(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
@@ -204,7 +252,25 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
         return 2;
     }
     std::cout << std::chrono::duration_cast<std::chrono::milliseconds>(wallDiff).count() << "\n";
-    for (int64_t i = 0; i < npairs; ++i) std::cout << "Score: " << scores[(size_t)i] << "\n";
+    for (int64_t i = 0; i < npairs && !local; ++i) std::cout << "Score: " << scores[(size_t)i] << "\n";
+    for (int64_t i = 0; i < npairs && local; ++i) {
+        const nw_local_hit &h = hits[(size_t)i];
+        std::cout << "Score: " << h.score;
+        if (!score_only) std::cout << " begin (" << h.begin_i << ", " << h.begin_j << ")";
+        std::cout << " end (" << h.end_i << ", " << h.end_j << ")\n";
+        if (score_only) continue;
+        const int64_t n = n_ops[(size_t)i], n1 = off1[(size_t)i + 1] - off1[(size_t)i],
+                      n2 = off2[(size_t)i + 1] - off2[(size_t)i];
+        std::vector<int8_t> row1((size_t)n + 1), row2((size_t)n + 1);
+        if (nw_ops_expand(s1cat.data() + off1[(size_t)i], n1, s2cat.data() + off2[(size_t)i], n2, h.begin_i, h.begin_j,
+                          ops.data() + ops_off[(size_t)i], n, row1.data(), row2.data()) != NW_OK) {
+            std::fprintf(stderr, "nw_align (libnwhip): inconsistent ops\n");
+            return 2;
+        }
+        row1.resize((size_t)n);
+        row2.resize((size_t)n);
+        std::cout << "A: " << row_text(row1) << "\nB: " << row_text(row2) << "\n";
+    }
     std::cout.flush();
     return 0;
 }
@@ -218,7 +284,7 @@ int main(int argc, char **argv) {
     bool ckpt = false, score_only = false;
     const char *batch = nullptr, *matrix = nullptr;
     int32_t gap_open = 0;
-    bool affine = false;
+    bool affine = false, local = false;
     for (int a = 1; a < argc; ++a) {
         if (std::strcmp(argv[a], "--scheme") == 0) {
             int m, mm, g;
@@ -254,6 +320,8 @@ int main(int argc, char **argv) {
                 return 1;
             }
             matrix = argv[++a];
+        } else if (std::strcmp(argv[a], "--local") == 0) {
+            local = true;
         } else if (std::strcmp(argv[a], "--score-only") == 0) {
             score_only = true;
         } else if (std::strcmp(argv[a], "--batch") == 0) {
@@ -269,11 +337,22 @@ int main(int argc, char **argv) {
     if (batch != nullptr) {
         if (!pos.empty() || co.block_rows != 0) {
             std::cout << "error: --batch takes the list alone (and --scheme, --mem, --score-only, --gap-open, "
-                         "--matrix)"
+                         "--matrix, --local)"
                       << std::endl;
             return 1;
         }
-        return run_batch(batch, p, co.mem_bytes, score_only, affine ? &gap_open : nullptr, matrix);
+        if (local) {
+            if (p.gap > 0) {
+                std::cout << "error: --local needs a gap of at most 0 (--scheme's third number)" << std::endl;
+                return 1;
+            }
+            p.mode = NW_MODE_SW;
+        }
+        return run_batch(batch, p, co.mem_bytes, score_only, affine ? &gap_open : nullptr, matrix, local);
+    }
+    if (local) {
+        std::cout << "error: --local needs --batch (the one-pair local alignment is nw_sw_align's)" << std::endl;
+        return 1;
     }
     if (matrix != nullptr) {
         std::cout << "error: --matrix needs --batch (substitution matrices are built for the batched alignment only)"

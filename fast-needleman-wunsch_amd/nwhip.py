@@ -43,7 +43,8 @@ EXPORTS = ["nw_params_default", "nw_strerror", "nw_version", "nw_fill", "nw_tabl
            "nw_batch_dir_bytes", "nw_score_batch_async", "nw_score_batch", "nw_align_batch",
            "nw_batch_affine_dir_bytes", "nw_score_batch_affine_async", "nw_score_batch_affine",
            "nw_align_batch_affine", "nw_ops_score_affine",
-           "nw_score_batch_matrix_async", "nw_score_batch_matrix", "nw_align_batch_matrix", "nw_ops_score_matrix"]
+           "nw_score_batch_matrix_async", "nw_score_batch_matrix", "nw_align_batch_matrix", "nw_ops_score_matrix",
+           "nw_score_batch_local_async", "nw_score_batch_local", "nw_align_batch_local"]
 IPC_HANDLE_BYTES = 64
 
 
@@ -119,6 +120,17 @@ class NwSubmat(ctypes.Structure):
 
 CKPT_TAG = 1   # NW_CKPT_TAG: the tag of every checkpoint granule (nw_band.tag of a re-fill)
 TB_NO_AIM = 1  # nw_tb_opts.flags NW_TB_NO_AIM: diagonal rounds instead of rounds aimed at (0, 0)
+
+
+class NwLocalHit(ctypes.Structure):
+    """nw_local_hit (include/nw_hip.h): the best local alignment of one pair of a batch."""
+    _fields_ = [("score", ctypes.c_int32), ("end_i", ctypes.c_int32), ("end_j", ctypes.c_int32),
+                ("begin_i", ctypes.c_int32), ("begin_j", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+# the same 32 bytes as a numpy record (score_batch_local, align_batch_local)
+LOCAL_HIT_DTYPE = np.dtype([("score", np.int32), ("end_i", np.int32), ("end_j", np.int32), ("begin_i", np.int32),
+                            ("begin_j", np.int32), ("reserved", np.int32, (3,))])
 
 
 class NwBand(ctypes.Structure):
@@ -254,6 +266,13 @@ def lib() -> ctypes.CDLL:
     L.nw_ops_score_matrix.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                       _u8p, ctypes.c_int64, ctypes.POINTER(NwParams), _smp, ctypes.c_int32,
                                       ctypes.POINTER(ctypes.c_int64)]
+    _lhp = ctypes.POINTER(NwLocalHit)
+    L.nw_score_batch_local_async.argtypes = L.nw_score_batch_matrix_async.argtypes
+    L.nw_score_batch_local.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams), _smp,
+                                       ctypes.c_int32, _lhp, ctypes.POINTER(NwBatchStats)]
+    L.nw_align_batch_local.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams), _smp,
+                                       ctypes.c_int32, ctypes.POINTER(NwBatchOpts), _lhp, _u8p, _i64p_, _i64p_,
+                                       ctypes.POINTER(NwBatchStats)]
     L.nw_debug_tb_shift.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                     ctypes.c_int64]
     L.nw_debug_tb_shift.restype = ctypes.c_int64
@@ -674,6 +693,24 @@ class SubMatrix:
                 raise ValueError(f"byte {int(s[bad][0])} is not a letter of the matrix (pass other=)")
 
     @classmethod
+    def uniform(cls, letters, match: int, mismatch: int, other=None):
+        """The match / mismatch matrix over `letters`: `match` on the diagonal, `mismatch`
+        elsewhere.  other: one more letter, added to them, that every unlisted byte maps
+        to and that scores `mismatch` against everything, itself included (N against N is
+        no match)."""
+        if isinstance(letters, (str, bytes, bytearray)):
+            letters = list(letters)
+        letters = [_letter_byte(t) for t in letters]
+        if other is not None:
+            letters = letters + [_letter_byte(other)]
+        n = len(letters)
+        sc = np.full((n, n), int(mismatch), np.int64)
+        sc[np.arange(n), np.arange(n)] = int(match)
+        if other is not None:
+            sc[n - 1, n - 1] = int(mismatch)
+        return cls(letters, sc, None if other is None else letters[-1])
+
+    @classmethod
     def from_text(cls, path_or_str, other=None):
         """The usual NCBI text layout: '#' comment lines, a header row of letters, then one
         row per letter (its letter, then n integers): the entry of row r, column c is
@@ -751,6 +788,55 @@ def align_batch_matrix(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, 
         raise NwError(st, "nw_align_batch_matrix")
     out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
     return scores[:n], out, stats
+
+
+def score_batch_local(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, waves: int = 0, device: int = -1,
+                      return_stats: bool = False):
+    """Batched local alignment scores (nw_score_batch_local): Smith-Waterman under affine
+    gap cost with substitution by `mat`.  Returns a LOCAL_HIT_DTYPE array, one record per
+    pair: score, end_i, end_j (the first row-major maximum; (0, 0) when the score is 0)
+    and begin_i = begin_j = -1 (the score entry finds no begin cell)."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    mat.check(s1, s2)
+    n = len(pairs)
+    hits = np.zeros(max(n, 1), LOCAL_HIT_DTYPE)
+    stats = NwBatchStats()
+    p = params((1, 0, int(gap)), waves, device, mode=MODE_SW)
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_score_batch_local(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
+                                    off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
+                                    int(gap_open), hits.ctypes.data_as(ctypes.POINTER(NwLocalHit)),
+                                    ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_score_batch_local")
+    return (hits[:n], stats) if return_stats else hits[:n]
+
+
+def align_batch_local(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, mem_bytes: int = 0, waves: int = 0,
+                      device: int = -1):
+    """Batched local alignments (nw_align_batch_local): (hits, [ops of pair 0, ..],
+    NwBatchStats).  hits as score_batch_local with the begin cells filled in; a pair's ops
+    (0 diag, 1 up, 2 left) lead from its begin cell to its end cell."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    mat.check(s1, s2)
+    n = len(pairs)
+    ops_off = off1 + off2
+    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
+    hits = np.zeros(max(n, 1), LOCAL_HIT_DTYPE)
+    n_ops = np.zeros(max(n, 1), np.int64)
+    stats = NwBatchStats()
+    p = params((1, 0, int(gap)), waves, device, mode=MODE_SW)
+    o = NwBatchOpts(int(mem_bytes))
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_align_batch_local(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
+                                    off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
+                                    int(gap_open), ctypes.byref(o), hits.ctypes.data_as(ctypes.POINTER(NwLocalHit)),
+                                    ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                    ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_align_batch_local")
+    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
+    return hits[:n], out, stats
 
 
 def ops_score_matrix(s1, s2, ops, mat: SubMatrix, gap: int = -1, gap_open: int = 0, begin=(0, 0)) -> int:
@@ -1357,6 +1443,34 @@ class Context:
             raise ValueError("Context.score_batch_matrix needs a matrix with other= (it cannot check the sequences)")
         return self.score_batch(d_s1cat, d_off1, d_s2cat, d_off2, max_n2, (1, 0, int(gap)), stream, waves, 0,
                                 gap_open=int(gap_open), mat=mat)
+
+    def score_batch_local(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, mat: SubMatrix, gap: int = -1,
+                          gap_open: int = 0, stream=None, waves: int = 0):
+        """Local alignment hits of a batch on device tensors (nw_score_batch_local_async):
+        the arguments of Context.score_batch_matrix.  Returns an int32 CUDA tensor (npairs,
+        8), a row in nw_local_hit's layout: score, end_i, end_j, begin_i = begin_j = -1,
+        three zeros; a pair longer than max_n2: INT32_MIN and -1 in the four coordinates.
+        Ordered on `stream`; nothing is synchronised."""
+        import torch
+        if mat.other is None and not mat.listed.all():
+            raise ValueError("Context.score_batch_local needs a matrix with other= (it cannot check the sequences)")
+        npairs = int(d_off1.numel()) - 1
+        assert d_off1.dtype == torch.int64 and d_off2.dtype == torch.int64 and int(d_off2.numel()) == npairs + 1
+        assert d_off1.is_contiguous() and d_off2.is_contiguous()
+        t1, t2 = int(d_s1cat.numel()), int(d_s2cat.numel())
+        if stream is None:
+            stream = torch.cuda.current_stream(d_off1.device)
+        with torch.cuda.stream(stream):
+            hits = torch.zeros((max(npairs, 1), 8), dtype=torch.int32, device=d_off1.device)
+        p = params((1, 0, int(gap)), waves, self.device, mode=MODE_SW)
+        st = lib().nw_score_batch_local_async(
+            self._h, ctypes.c_void_p(d_s1cat.data_ptr() if t1 else 0), ctypes.c_void_p(d_off1.data_ptr()),
+            ctypes.c_void_p(d_s2cat.data_ptr() if t2 else 0), ctypes.c_void_p(d_off2.data_ptr()), npairs, t1, t2,
+            int(max_n2), ctypes.byref(p), ctypes.byref(mat.c), int(gap_open), ctypes.c_void_p(hits.data_ptr()),
+            ctypes.c_void_p(stream.cuda_stream))
+        if st != NW_OK:
+            raise NwError(st, "nw_score_batch_local_async")
+        return hits[:npairs]
 
     def traceback_block(self, d_s1, d_s2_block, table, row0: int, scheme=(1, 0, -1), stream=None, band: int = 0,
                         max_windows: int = 0, no_aim: bool = False):

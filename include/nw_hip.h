@@ -559,6 +559,61 @@ int nw_align_batch_matrix(const int8_t *s1cat, const int64_t *off1, const int8_t
                           const nw_batch_opts *o, int32_t *scores, uint8_t *ops, const int64_t *ops_off,
                           int64_t *n_ops, nw_batch_stats *stats);
 
+/* Batched LOCAL alignment (Smith-Waterman) with affine gaps and a matrix ---------
+ * The best-scoring pair of substrings of every pair of a batch: a read against a
+ * reference window, a protein against a database hit.  Substitution, the nw_submat and
+ * its validity rules, gap_open (<= 0) and nw_params.gap as the extension ge are exactly
+ * those of the matrix entries above.  The recurrence is Gotoh's with a floor of zero
+ * and free ends:
+ *   E[i][j] = max(E[i][j-1] + ge, H[i][j-1] + go + ge)
+ *   F[i][j] = max(F[i-1][j] + ge, H[i-1][j] + go + ge)
+ *   H[i][j] = max(0, H[i-1][j-1] + s(s1[j-1], s2[i-1]), F[i][j], E[i][j])
+ *   H[0][j] = H[i][0] = 0,   E[i][0] = F[0][j] = -inf
+ * score = the maximum of H over the whole table; the end cell is the maximising cell
+ * with the smallest i and among those the smallest j (first in row-major order, as
+ * nw_sw_align).  When the maximum is 0, end = begin = (0, 0) and n_ops = 0; a pair
+ * with an empty side gives the same.  The ops are the walk of the affine entries'
+ * machine of three states, started at the end cell in state H, with one more rule that
+ * is checked first: in state H at a cell with H == 0 (every cell of row 0 and column 0
+ * is one) the walk stops, and that cell is the begin cell.  Otherwise the first of
+ * diag, F, E that equals H is taken; in F and E opening wins a tie over extending.  Ops
+ * are 0 diag / 1 up / 2 left in path order begin -> end, n_ops <= n1 + n2, and
+ * nw_ops_score_matrix(..., begin_i, begin_j, ...) of them equals the score.  With
+ * gap_open = 0 and a match / mismatch matrix the score, both cells and the ops are
+ * nw_sw_align's (tie order diag > up > left).
+ * CSR layout, options, statistics, slot sizes (n1 + n2 bytes), longest-first tickets,
+ * chunking by mem_bytes, nw_batch_affine_dir_bytes and NW_ERR_OOM for a pair that does
+ * not fit alone are the matrix entries'.  So are the refusals and their order, with the
+ * hits in the place of the scores and p->mode required to be NW_MODE_SW (which refuses
+ * gap > 0; p == NULL: the defaults with mode NW_MODE_SW), and the range:
+ *   3*|gap_open| + (M + |gap|) * (n1 + n2 + 2) < 2^28
+ * unchanged, conservative for a local table.  In the _async form a pair longer than
+ * max_n2 gets score INT32_MIN and -1 in the four coordinates; empty pairs are answered
+ * by the kernel.  The score entries find no begin cell (that needs a reverse sweep)
+ * and write -1.  Nothing per pair crosses to the host between the sweep and the walk:
+ * the sweep writes the hit, the walk reads its start from it on the device (kernels:
+ * csrc/nw_batch_local.hip). */
+typedef struct nw_local_hit {      /* 32 bytes */
+    int32_t score;                 /* max H, >= 0                                    */
+    int32_t end_i, end_j;          /* first row-major maximum; (0,0) when score == 0 */
+    int32_t begin_i, begin_j;      /* align entry: where the walk stopped; score entries: -1 */
+    int32_t reserved[3];           /* written as 0 */
+} nw_local_hit;
+
+int nw_score_batch_local_async(nw_ctx *ctx, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                               const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2,
+                               int64_t max_n2, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                               nw_local_hit *d_hits, void *stream);
+
+int nw_score_batch_local(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                         int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                         nw_local_hit *hits, nw_batch_stats *stats);
+
+int nw_align_batch_local(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                         int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                         const nw_batch_opts *o, nw_local_hit *hits, uint8_t *ops, const int64_t *ops_off,
+                         int64_t *n_ops, nw_batch_stats *stats);
+
 /* Launch-only variant for timing loops: no synchronisation, no readback. */
 int nw_fill_device_async(nw_ctx *ctx, const int8_t *d_s1, int64_t n1,
                          const int8_t *d_s2, int64_t n2, const nw_params *p,

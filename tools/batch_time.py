@@ -23,6 +23,15 @@ library's one-pair path, unchanged by the batch; its scores must equal the batch
                     yardstick: code the matrix does not touch) and the two ratios.  Writes
                     profiles/batch_matrix_time.json.
 
+  --local           the local entries (nw_score_batch_local, nw_align_batch_local) on pairs over 20
+                    letters under a seeded symmetric matrix whose expected score on random
+                    letters is negative (3..11 on the diagonal, -6..1 off it), gap -1 and
+                    --gap-open (default -11); every pair holds a planted segment: a stretch of
+                    s1 (a quarter to three quarters of the shorter side) stands in s2 with 10 %
+                    substitutions and an indel run of 1..20 every 60 letters or so.  In the
+                    same process the global matrix entries on the SAME pairs and matrix (the
+                    yardstick) and the ratios.  Writes profiles/batch_local_time.json.
+
 The score kernel's yardstick is the checkpoint sweep's pace on one huge table
 (profiles/ckpt_time.json: 262144^2 in 20.62 ms); `fraction_of_sweep_pace` states it.
 """
@@ -50,12 +59,16 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--loop-reps", type=int, default=5)
 ap.add_argument("--gap-open", type=int, default=None)
 ap.add_argument("--matrix", type=int, default=None, nargs="?", const=20)
+ap.add_argument("--local", action="store_true")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
+if args.local:
+    args.matrix = 20
 if args.matrix is not None and args.gap_open is None:
     args.gap_open = -11
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "batch_matrix_time.json" if args.matrix is not None else
+    args.out = os.path.join(ROOT, "profiles", "batch_local_time.json" if args.local else
+                            "batch_matrix_time.json" if args.matrix is not None else
                             "batch_time.json" if args.gap_open is None else "batch_affine_time.json")
 scheme = (1, 0, -1)
 med = statistics.median
@@ -90,7 +103,45 @@ def make_matrix(n):
     return letters, nwhip.SubMatrix(letters.tolist(), sc, other=int(letters[0]))
 
 
-def time_entries(pairs, cells, score_f, align_f):
+def make_local_matrix(n):
+    """make_matrix's alphabet under a seeded symmetric matrix of negative expected score."""
+    rng = np.random.default_rng(162 + n)
+    letters = np.sort(np.random.default_rng(62 + n).choice(np.arange(1, 128), n, replace=False)).astype(np.int8)
+    sc = rng.integers(-6, 2, (n, n))
+    sc = np.triu(sc, 1) + np.triu(sc, 1).T + np.diag(rng.integers(3, 12, n))
+    assert sc.mean() < -1
+    return letters, nwhip.SubMatrix(letters.tolist(), sc, other=int(letters[0]))
+
+
+def plant_segments(pairs, letters, seed):
+    """Into every s2 a mutated copy of a stretch of its s1."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for a, b in pairs:
+        b = b.copy()
+        m = min(a.size, b.size)
+        seg = int(rng.integers(m // 4, 3 * m // 4 + 1))
+        src = a[int(rng.integers(0, a.size - seg + 1)):][:seg].copy()
+        hit = rng.random(seg) < 0.1
+        src[hit] = letters[rng.integers(0, len(letters), int(hit.sum()))]
+        parts, at = [], 0
+        while at < seg:
+            nxt = min(seg, at + int(rng.integers(40, 81)))
+            parts.append(src[at:nxt])
+            run = int(rng.integers(1, 21))
+            if rng.random() < 0.5:
+                parts.append(letters[rng.integers(0, len(letters), run)])  # ups
+                at = nxt
+            else:
+                at = nxt + run                                            # lefts
+        cp = np.concatenate(parts)[:b.size]
+        at2 = int(rng.integers(0, b.size - cp.size + 1))
+        b[at2:at2 + cp.size] = cp
+        out.append((a, b))
+    return out
+
+
+def time_entries(pairs, cells, score_f, align_f, key=lambda r: r):
     """(score entry, align entry, scores): medians of --reps calls after a warm-up each."""
     score_f(pairs, return_stats=True)
     rs = [wall(lambda: score_f(pairs, return_stats=True)) for _ in range(args.reps)]
@@ -102,7 +153,7 @@ def time_entries(pairs, cells, score_f, align_f):
     ra = [wall(lambda: align_f(pairs)) for _ in range(args.reps)]
     st = ra[0][1][2]
     afill, awalk = med(r[1][2].fill_ms for r in ra), med(r[1][2].walk_ms for r in ra)
-    assert np.array_equal(ra[0][1][0], scores)
+    assert np.array_equal(key(ra[0][1][0]), key(scores))
     ae = {"fill_ms": round(afill, 3), "walk_ms": round(awalk, 3), "fill_walk_ms": round(afill + awalk, 3),
           "wall_ms": round(med(r[0] for r in ra), 3), "gcups_kernel": round(cells / (afill * 1e6), 1),
           "gcups_fill_walk": round(cells / ((afill + awalk) * 1e6), 1), "chunks": int(st.chunks),
@@ -152,6 +203,29 @@ def run_matrix(name):
     return e
 
 
+def run_local(name):
+    go, ge = args.gap_open, -1
+    letters, mat = make_local_matrix(20)
+    pairs = plant_segments(make_pairs(name, letters), letters, 7 + len(name))
+    cells = sum(a.size * b.size for a, b in pairs)
+    e = {"shape": name, "pairs": len(pairs), "cells": int(cells), "gap_open": go, "gap": ge, "letters": 20,
+         "matrix_entries": [int(mat.scores.min()), int(mat.scores.max())],
+         "matrix_mean": round(float(mat.scores.mean()), 2),
+         "lengths": "uniform %d..%d" % SHAPES[name][1:] if name == "mixed" else "%d x %d" % SHAPES[name][1:]}
+    gs, ga, _ = time_entries(pairs, cells, lambda p, **kw: nwhip.score_batch_matrix(p, mat, ge, go, **kw),
+                             lambda p: nwhip.align_batch_matrix(p, mat, ge, go))
+    s, a, hits = time_entries(pairs, cells, lambda p, **kw: nwhip.score_batch_local(p, mat, ge, go, **kw),
+                              lambda p: nwhip.align_batch_local(p, mat, ge, go), key=lambda h: h["score"])
+    e["median_local_score"] = int(np.median(hits["score"]))
+    e["score_batch_matrix"], e["align_batch_matrix"] = gs, ga
+    e["score_batch_local"], e["align_batch_local"] = s, a
+    e["score_local_over_matrix"] = round(s["fill_ms"] / gs["fill_ms"], 2)
+    e["align_fill_local_over_matrix"] = round(a["fill_ms"] / ga["fill_ms"], 2)
+    e["align_fill_walk_local_over_matrix"] = round(a["fill_walk_ms"] / ga["fill_walk_ms"], 2)
+    print(json.dumps(e), flush=True)
+    return e
+
+
 def run(name):
     pairs = make_pairs(name)
     cells = sum(a.size * b.size for a, b in pairs)
@@ -196,7 +270,7 @@ if os.path.exists(args.out):
 rec.update({"device": torch.cuda.get_device_name(0), "library": nwhip.version(), "scheme": list(scheme),
             "reps": args.reps, "sweep_yardstick_gcups": round(SWEEP_GCUPS, 1)})
 for name in (list(SHAPES) if args.shape == "all" else [args.shape]):
-    rec["shapes"][name] = (run_matrix(name) if args.matrix is not None else
+    rec["shapes"][name] = (run_local(name) if args.local else run_matrix(name) if args.matrix is not None else
                            run(name) if args.gap_open is None else run_affine(name))
 os.makedirs(os.path.dirname(args.out), exist_ok=True)
 with open(args.out, "w") as f:
