@@ -155,18 +155,22 @@ void batch_order(const int64_t *off1, const int64_t *off2, int64_t npairs, Batch
     std::stable_sort(b->order.begin(), b->order.end(), [&](int32_t x, int32_t y) { return cells(x) > cells(y); });
 }
 
+// the workers of a launch: nw_params.waves (0: kCkptWavesPerCU per CU) capped at `tickets`
+int64_t workers(const nw_ctx *c, const nw_params *p, int64_t tickets) {
+    const int64_t w = p->waves > 0 ? p->waves : (int64_t)c->cus * nw::kCkptWavesPerCU;
+    return std::max<int64_t>(1, std::min<int64_t>(w, tickets));
+}
+
 // The context's workspace of a batch launch, the charmap over the concatenated s1 and
 // the row characters of the concatenated s2 (three small launches per batch, whatever
 // its number of pairs; with a matrix: one launch, the rows as letters, and the matrix
 // into *ma); *ma gets everything but the tickets, the scores and the
-// directions, *grid the workers (nw_params.waves; 0: kCkptWavesPerCU per CU) capped at
-// `tickets`.
+// directions, *grid the workers.
 int batch_prepare(nw_ctx *c, const int8_t *d_s1, const int64_t *d_off1, int64_t total1, const int8_t *d_s2,
                   const int64_t *d_off2, int64_t total2, int64_t max_n2, const nw_params *p, const Cost &cost,
                   int64_t tickets, void *stream, nw::BatchMatrixArgs *ma, int *grid) {
     int st;
-    int64_t waves = p->waves > 0 ? p->waves : (int64_t)c->cus * nw::kCkptWavesPerCU;
-    waves = std::max<int64_t>(1, std::min<int64_t>(waves, tickets));
+    const int64_t waves = workers(c, p, tickets);
     const int64_t cstride = cost.col_words(max_n2);
     const int64_t rows_len = nw::kBatchRowPad + total2 + nw::kBatchRowTail;
     if ((st = grow((void **)&c->rowpack, &c->rowpack_cap, (size_t)rows_len)) != NW_OK) return st;
@@ -263,11 +267,6 @@ struct BatchDev {
 int64_t workspace_need(const Batch &b, int64_t waves, const Cost &cost) {
     return nw::kBatchRowPad + b.total2 + nw::kBatchRowTail + waves * cost.col_words(b.max_n2) * 4 +
            nw::kMetaBytes + nw::kCtrlWords * 4;
-}
-
-int64_t workers(const nw_ctx *c, const nw_params *p, int64_t tickets) {
-    const int64_t w = p->waves > 0 ? p->waves : (int64_t)c->cus * nw::kCkptWavesPerCU;
-    return std::max<int64_t>(1, std::min<int64_t>(w, tickets));
 }
 
 int score_batch_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,

@@ -101,6 +101,8 @@ int launch_batch_rows(const uint8_t *d_s2, int64_t total2, int32_t perm, const u
 int launch_batch(const BatchArgs &a, bool dirs, int grid, void *stream);
 // the walk (ops end -> begin, n_ops), then the reversal into begin -> end order
 int launch_batch_walk(const BatchWalkArgs &w, void *stream);
+// the reversal alone (nw_batch.hip nw_batch_reverse): what every walk below ends with
+int launch_batch_reverse(const BatchWalkArgs &w, void *stream);
 // the same two for affine gaps: the walk is a machine of three states over 4 bits per cell
 int launch_batch_affine(const BatchAffineArgs &a, bool dirs, int grid, void *stream);
 int launch_batch_affine_walk(const BatchWalkArgs &w, void *stream);

@@ -22,21 +22,21 @@
 // a lane's step into a byte and four steps into a dword, stored step-major
 // ([strip][step / 4][lane]): every store instruction writes 256 contiguous bytes.
 // nw_batch_walk inverts that mapping, one thread per pair.
+//
+// load_rows, uniform64 and claim_ticket are nw_batch_dev.h's, shared with the affine
+// family's files; the sweep itself is this file's own (one value per column, 2 bits per
+// cell, no E and no F: that header's skeleton does not fit it).  nw_batch_reverse, here,
+// serves every walk of the batch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <type_traits>
 
-#include "nw_batch.h"
-#include "nw_dev.h"
-#include "nw_internal.h"
-#include "nw_strips.h"  // (diag_plus_sub, u32x4)
+#include "nw_batch_dev.h"  // (load_rows, uniform64, claim_ticket; nw_strips.h diag_plus_sub)
 
 namespace nw {
 namespace {
-
-constexpr int C = kCkptC;
 
 struct BatchLane {
     int32_t u[C];     // w of the lane's current row, column k
@@ -47,14 +47,6 @@ struct BatchLane {
     int32_t fv;       // feed: lane x holds the left strip's right column at row 64it + x
     int32_t acc;      // right column gathered: lane x holds row 64(it-1) + x
 };
-
-// Row characters of iteration j: lane l needs the bytes of rows 64j - l + u, u < 64
-// (rowb[y] = row y's character).  The four 16-byte loads are unaligned.
-__device__ __forceinline__ void load_rows(const uint8_t *__restrict__ rowb, int j, int lane, u32x4 (&pk)[4]) {
-    const uint8_t *b = rowb + (int64_t)j * 64 - lane;
-#pragma unroll
-    for (int h = 0; h < 4; ++h) __builtin_memcpy(&pk[h], b + 16 * h, 16);
-}
 
 // 64 steps of iteration `it` (steps 64it + u): lane l computes row 64it + u - l.
 //   EDGE : some lane's row is outside 1..n2 in this iteration (it holds its cells)
@@ -113,16 +105,6 @@ __device__ __forceinline__ void batch_iter(int it, const u32x4 (&pk)[4], int32_t
         });
         if constexpr (DIRS) dq[gi * kWave] = dw;
     });
-}
-
-// A value every lane holds alike, moved to scalar registers: the pair's offsets and
-// lengths are loaded with vector loads (the arrays are not known to be read-only),
-// and loop bounds left in vector registers would make every loop of the sweep a
-// divergent one.
-__device__ __forceinline__ int64_t uniform64(int64_t v) {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
 // One pair (n1, n2 >= 1), all its strips, by this wave.  s1: the pair's column
@@ -196,17 +178,6 @@ __device__ __forceinline__ void batch_pair(const BatchArgs &A, const uint8_t *__
                 if (cl + k == n1) *score = S.u[k] + gap * (n2 + n1);
         }
     }
-}
-
-// The next ticket, in every lane.  Kept out of line: inlined into the ticket loop,
-// `lane == 0` is a loop invariant and the optimiser unswitches the loop on it; the
-// copy for the other lanes then runs beside lane 0's with a constant ticket 0 (in the
-// ISA: a second loop that loads order[0]; on the device: now and then a wrong score
-// for the pair of ticket 0).  A call is opaque to that.
-__device__ __noinline__ int claim_ticket(uint32_t *ticket) {
-    uint32_t t = 0;
-    if ((threadIdx.x & 63) == 0) t = atomicAdd(ticket, 1u);
-    return (int)__builtin_amdgcn_readfirstlane(t);
 }
 
 // Persistent grid of one-wave workgroups; pairs claimed in order from the ticket.
@@ -302,7 +273,8 @@ __global__ __launch_bounds__(64) void nw_batch_walk(BatchWalkArgs W) {
     W.n_ops[t] = n;
 }
 
-// ops of ticket blockIdx.x into begin -> end order
+// ops of ticket blockIdx.x into begin -> end order: after any of the batch's walks
+// (launch_batch_reverse)
 __global__ __launch_bounds__(64) void nw_batch_reverse(BatchWalkArgs W) {
     const int t = blockIdx.x;
     uint8_t *ops = W.ops + W.ops_off[t];
@@ -333,10 +305,14 @@ int launch_batch(const BatchArgs &a, bool dirs, int grid, void *stream) {
     return (int)hipGetLastError();
 }
 
-int launch_batch_walk(const BatchWalkArgs &w, void *stream) {
-    hipLaunchKernelGGL(nw_batch_walk, dim3((unsigned)((w.npairs + 63) / 64)), dim3(64), 0, (hipStream_t)stream, w);
+int launch_batch_reverse(const BatchWalkArgs &w, void *stream) {
     hipLaunchKernelGGL(nw_batch_reverse, dim3((unsigned)w.npairs), dim3(64), 0, (hipStream_t)stream, w);
     return (int)hipGetLastError();
+}
+
+int launch_batch_walk(const BatchWalkArgs &w, void *stream) {
+    hipLaunchKernelGGL(nw_batch_walk, dim3((unsigned)((w.npairs + 63) / 64)), dim3(64), 0, (hipStream_t)stream, w);
+    return launch_batch_reverse(w, stream);
 }
 
 }  // namespace nw

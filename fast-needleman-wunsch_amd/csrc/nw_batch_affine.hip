@@ -28,22 +28,21 @@
 // bits, four steps two dwords, stored [strip][iteration][step / 4][step % 4 / 2][lane]:
 // every store instruction writes 256 contiguous bytes.  nw_batch_affine_walk inverts
 // that mapping, one thread per pair.
+//
+// nw_batch_matrix.hip and nw_batch_local.hip run this decomposition from one skeleton
+// (nw_batch_dev.h sweep_tickets / sweep_pair / sweep_iter).  This file's sweep is NOT on
+// it: on the skeleton the score kernel came out 0.7 % slower at 8000 x 8000, from an ISA
+// that differed in a few swapped instructions, so affine_iter, affine_pair and the
+// ticket loop stand here in their own text and compile to the ISA they had before the
+// skeleton existed.  From that header come load_rows, uniform64, claim_ticket and the
+// index of a cell's direction bits (NW_DIR_NIBBLE); the reversal is nw_batch.hip's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-#include <type_traits>
-
-#include "nw_batch.h"
-#include "nw_dev.h"
-#include "nw_internal.h"
-#include "nw_strips.h"  // (diag_plus_sub, u32x4)
+#include "nw_batch_dev.h"
 
 namespace nw {
 namespace {
-
-constexpr int C = kCkptC;
-constexpr int32_t kNegInf = -(1 << 29);
 
 struct AffineLane {
     int32_t u[C];     // H' of the lane's current row, column k
@@ -56,14 +55,6 @@ struct AffineLane {
     int32_t fvh, fve;  // feed: lane x holds H' / E' of the left strip's right column at row 64it + x
     int32_t acch, acce;  // right column gathered: lane x holds row 64(it-1) + x
 };
-
-// Row characters of iteration j: lane l needs the bytes of rows 64j - l + u, u < 64
-// (rowb[y] = row y's character).  The four 16-byte loads are unaligned.
-__device__ __forceinline__ void load_rows(const uint8_t *__restrict__ rowb, int j, int lane, u32x4 (&pk)[4]) {
-    const uint8_t *b = rowb + (int64_t)j * 64 - lane;
-#pragma unroll
-    for (int h = 0; h < 4; ++h) __builtin_memcpy(&pk[h], b + 16 * h, 16);
-}
 
 // 64 steps of iteration `it` (steps 64it + u): lane l computes row 64it + u - l.
 //   EDGE : some lane's row is outside 1..n2 in this iteration (it holds its cells)
@@ -149,13 +140,6 @@ __device__ __forceinline__ void affine_iter(int it, const u32x4 (&pk)[4], int32_
             dq[(2 * gi + 1) * kWave] = dw[1];
         }
     });
-}
-
-// (nw_batch.hip uniform64)
-__device__ __forceinline__ int64_t uniform64(int64_t v) {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
 // One pair (n1, n2 >= 1), all its strips, by this wave.  s1: the pair's column
@@ -249,15 +233,6 @@ __device__ __forceinline__ void affine_pair(const BatchAffineArgs &AA, const uin
     }
 }
 
-// The next ticket, in every lane.  Kept out of line, as nw_batch.hip's claim_ticket
-// (inlined, the optimiser unswitches the ticket loop on `lane == 0` and the copy for
-// the other lanes runs with a constant ticket 0).
-__device__ __noinline__ int claim_ticket_affine(uint32_t *ticket) {
-    uint32_t t = 0;
-    if ((threadIdx.x & 63) == 0) t = atomicAdd(ticket, 1u);
-    return (int)__builtin_amdgcn_readfirstlane(t);
-}
-
 // Persistent grid of one-wave workgroups; pairs claimed in order from the ticket.
 template <bool DIRS>
 __global__ __launch_bounds__(64) void nw_batch_affine_sweep(BatchAffineArgs AA) {
@@ -267,7 +242,7 @@ __global__ __launch_bounds__(64) void nw_batch_affine_sweep(BatchAffineArgs AA) 
     const bool perm = A.perm != 0 && np <= kMaxPerm;
     int32_t *col = A.colscr + (int64_t)blockIdx.x * A.cstride;
     for (;;) {
-        const int t = __builtin_amdgcn_readfirstlane(claim_ticket_affine(A.ticket));  // (a call returns in a vector register)
+        const int t = __builtin_amdgcn_readfirstlane(claim_ticket(A.ticket));  // (a call returns in a vector register)
         if (t >= A.npairs) break;
         int pair = t;
         if (A.order != nullptr) pair = __builtin_amdgcn_readfirstlane(A.order[t]);
@@ -323,12 +298,7 @@ __global__ __launch_bounds__(64) void nw_batch_affine_walk(BatchWalkArgs W) {
             c -= op != 1u;
             continue;
         }
-        const int64_t cj = c - 1;
-        const int64_t p = cj >> 8, l = (cj & 255) >> 2, k = cj & 3;
-        const int64_t s = r + l;
-        const int64_t idx =
-            ((((p * iters + (s >> 6)) * 16 + ((s & 63) >> 2)) * 2 + ((s & 3) >> 1)) * 64 + l) * 4 + (s & 1) * 2 + (k >> 1);
-        const uint32_t bits = ((uint32_t)d[idx] >> (4 * (k & 1))) & 15u;
+        NW_DIR_NIBBLE(bits, d, iters, r, c);
         if (state == 0) {
             state = bits & 3u;
             if (state == 0) {
@@ -349,18 +319,6 @@ __global__ __launch_bounds__(64) void nw_batch_affine_walk(BatchWalkArgs W) {
     W.n_ops[t] = n;
 }
 
-// ops of ticket blockIdx.x into begin -> end order (nw_batch.hip nw_batch_reverse)
-__global__ __launch_bounds__(64) void nw_batch_affine_reverse(BatchWalkArgs W) {
-    const int t = blockIdx.x;
-    uint8_t *ops = W.ops + W.ops_off[t];
-    const int64_t n = W.n_ops[t];
-    for (int64_t a = threadIdx.x; a < n / 2; a += 64) {
-        const uint8_t x = ops[a], y = ops[n - 1 - a];
-        ops[a] = y;
-        ops[n - 1 - a] = x;
-    }
-}
-
 }  // namespace
 
 int launch_batch_affine(const BatchAffineArgs &a, bool dirs, int grid, void *stream) {
@@ -374,8 +332,7 @@ int launch_batch_affine(const BatchAffineArgs &a, bool dirs, int grid, void *str
 int launch_batch_affine_walk(const BatchWalkArgs &w, void *stream) {
     hipLaunchKernelGGL(nw_batch_affine_walk, dim3((unsigned)((w.npairs + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
                        w);
-    hipLaunchKernelGGL(nw_batch_affine_reverse, dim3((unsigned)w.npairs), dim3(64), 0, (hipStream_t)stream, w);
-    return (int)hipGetLastError();
+    return launch_batch_reverse(w, stream);
 }
 
 }  // namespace nw
