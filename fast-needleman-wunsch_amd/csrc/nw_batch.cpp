@@ -12,7 +12,11 @@
 // entries (nw_score_batch_local_async, nw_score_batch_local, nw_align_batch_local; kernels
 // in nw_batch_local.hip) are the matrix ones in mode NW_MODE_SW: a pair's result is an
 // nw_local_hit where the others have an int32 score, the matrix goes into the arguments
-// as it is, and the walk starts at the hit the sweep left on the device.
+// as it is, and the walk starts at the hit the sweep left on the device.  The semi-global
+// entries (nw_score_batch_semi_async, nw_score_batch_semi, nw_align_batch_semi; kernels in
+// nw_batch_semi.hip) are the matrix ones with an `ends` set: mode, matrix bytes, range and
+// refusals as there, hits as the result like the local ones, and empty pairs answered here
+// from the definition.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -35,7 +39,10 @@ struct Cost {
     const nw_submat *mat = nullptr;
     int64_t mat_abs = 0;  // max |score[x][y]| over x, y < n
     bool local = false;   // Smith-Waterman (matrix is then true): a result is an nw_local_hit
-    size_t out_bytes() const { return local ? sizeof(nw_local_hit) : sizeof(int32_t); }
+    bool semi = false;    // free end gaps per side (matrix is then true): a result is an nw_local_hit
+    int32_t ends = 0;     // semi: NW_ENDS_* bits
+    bool hits() const { return local || semi; }
+    size_t out_bytes() const { return hits() ? sizeof(nw_local_hit) : sizeof(int32_t); }
     int64_t col_words(int64_t max_n2) const { return nw::batch_col_words(max_n2) * (affine ? 2 : 1); }
     int64_t dir_bytes(int64_t n1, int64_t n2) const {
         return affine ? nw_batch_affine_dir_bytes(n1, n2) : nw_batch_dir_bytes(n1, n2);
@@ -77,11 +84,49 @@ Cost local_cost(const nw_submat *m, int32_t gap_open) {
     return c;
 }
 
+Cost semi_cost(const nw_submat *m, int32_t gap_open, int32_t ends) {
+    Cost c = matrix_cost(m, gap_open);
+    c.semi = true;
+    c.ends = ends;
+    return c;
+}
+
 // the hit of a pair without cells, or whose best is 0: nothing aligned
 nw_local_hit empty_hit(int32_t begin) {
     nw_local_hit h;
     std::memset(&h, 0, sizeof h);
     h.begin_i = h.begin_j = begin;
+    return h;
+}
+
+// The semi-global hit of a pair with an empty side, from the definition: the table is one
+// boundary of n + 1 cells, B(0) = 0 and B(k) = 0 (its begin is free) or go + k * gap.  The
+// end is cell n, or with that boundary's end free the first maximum; the walk stops there
+// if the begin is free, else it runs to (0, 0).  walked: the align entry (begin cell and
+// *n_ops); the score entries write -1.
+nw_local_hit semi_empty_hit(const Cost &cost, const nw_params *p, int64_t n1, int64_t n2, bool walked,
+                            int64_t *n_ops) {
+    const bool rows = n1 == 0;  // the cells are (k, 0); else (0, k)
+    const int64_t n = std::max(n1, n2);
+    const bool begin_free = (cost.ends & (rows ? NW_ENDS_S2_BEGIN : NW_ENDS_S1_BEGIN)) != 0;
+    const bool end_free = (cost.ends & (rows ? NW_ENDS_S2_END : NW_ENDS_S1_END)) != 0;
+    auto B = [&](int64_t k) { return (k == 0 || begin_free) ? (int64_t)0 : (int64_t)cost.open + (int64_t)p->gap * k; };
+    int64_t k = n;
+    if (end_free) {  // (B is linear from 1 to n: the first maximum is at 0, 1 or n)
+        k = 0;
+        if (n >= 1 && B(1) > B(k)) k = 1;
+        if (B(n) > B(k)) k = n;
+    }
+    nw_local_hit h;
+    std::memset(&h, 0, sizeof h);
+    h.score = (int32_t)B(k);
+    (rows ? h.end_i : h.end_j) = (int32_t)k;
+    h.begin_i = h.begin_j = -1;
+    if (walked) {
+        h.begin_i = h.begin_j = 0;
+        if (begin_free) (rows ? h.begin_i : h.begin_j) = (int32_t)k;
+        *n_ops = begin_free ? 0 : k;
+    }
     return h;
 }
 
@@ -119,6 +164,7 @@ int params_check(const nw_params *p, int64_t npairs, const Cost &cost) {
     if (cost.affine && cost.open > 0) return NW_ERR_ARG;
     if (npairs < 0 || npairs >= INT32_MAX) return NW_ERR_ARG;
     if (cost.matrix && !valid_submat(cost.mat)) return NW_ERR_ARG;
+    if (cost.semi && (cost.ends < 0 || cost.ends > NW_ENDS_OVERLAP)) return NW_ERR_ARG;
     return NW_OK;
 }
 
@@ -211,8 +257,8 @@ int batch_prepare(nw_ctx *c, const int8_t *d_s1, const int64_t *d_off1, int64_t 
     return NW_OK;
 }
 
-// one launch of the batch kernel over a->npairs tickets (local: ma.a.b.scores holds the
-// hits)
+// one launch of the batch kernel over a->npairs tickets (local and semi: ma.a.b.scores
+// holds the hits)
 int batch_run(nw_ctx *c, const nw::BatchMatrixArgs &ma, const Cost &cost, bool dirs, int grid, void *stream) {
     if (nw::launch_ctrl_reset(c->ctrl, stream) != hipSuccess) return NW_ERR_HIP;
     const nw::BatchAffineArgs &aa = ma.a;
@@ -224,6 +270,13 @@ int batch_run(nw_ctx *c, const nw::BatchMatrixArgs &ma, const Cost &cost, bool d
         la.hits = ma.a.b.scores;
         la.m.a.b.scores = nullptr;
         e = nw::launch_batch_local(la, dirs, g, stream);
+    } else if (cost.semi) {
+        nw::BatchSemiArgs sa;
+        sa.m = ma;
+        sa.hits = ma.a.b.scores;
+        sa.m.a.b.scores = nullptr;
+        sa.ends = cost.ends;
+        e = nw::launch_batch_semi(sa, dirs, g, stream);
     } else
         e = cost.matrix ? nw::launch_batch_matrix(ma, dirs, g, stream)
             : cost.affine ? nw::launch_batch_affine(aa, dirs, g, stream)
@@ -294,7 +347,7 @@ int score_batch_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, c
 int score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2, int64_t npairs,
                 const nw_params *p, const Cost &cost, void *out, nw_batch_stats *stats) {
     int32_t *scores = (int32_t *)out;          // (global entries)
-    nw_local_hit *hits = (nw_local_hit *)out;  // (local entries)
+    nw_local_hit *hits = (nw_local_hit *)out;  // (local and semi-global entries)
     nw_params def;
     if (!p) {
         nw_params_default(&def);
@@ -319,6 +372,8 @@ int score_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
         if (n1 != 0 && n2 != 0) continue;
         if (cost.local)
             hits[i] = empty_hit(-1);
+        else if (cost.semi)
+            hits[i] = semi_empty_hit(cost, p, n1, n2, false, nullptr);
         else
             scores[i] = cost.empty_score(p, std::max(n1, n2));
     }
@@ -361,7 +416,7 @@ int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
                 const nw_params *p, const Cost &cost, const nw_batch_opts *o, void *out, uint8_t *ops,
                 const int64_t *ops_off, int64_t *n_ops, nw_batch_stats *stats) {
     int32_t *scores = (int32_t *)out;          // (global entries)
-    nw_local_hit *hits = (nw_local_hit *)out;  // (local entries)
+    nw_local_hit *hits = (nw_local_hit *)out;  // (local and semi-global entries)
     nw_params def;
     if (!p) {
         nw_params_default(&def);
@@ -402,6 +457,11 @@ int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
         if (cost.local) {  // nothing aligned
             hits[i] = empty_hit(0);
             n_ops[i] = 0;
+            continue;
+        }
+        if (cost.semi) {  // the part of the boundary between the begin and the end cell
+            hits[i] = semi_empty_hit(cost, p, n1, n2, true, &n_ops[i]);
+            if (n_ops[i] > 0) std::memset(ops + ops_off[i], n2 > 0 ? 1 : 2, (size_t)n_ops[i]);
             continue;
         }
         const int64_t n = std::max(n1, n2);
@@ -499,6 +559,12 @@ int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
             lw.w = w;
             lw.hits = d.scores;
             e = nw::launch_batch_local_walk(lw, nullptr);
+        } else if (cost.semi) {  // the same, stopping on a free boundary
+            nw::BatchSemiWalkArgs sw;
+            sw.w = w;
+            sw.hits = d.scores;
+            sw.ends = cost.ends;
+            e = nw::launch_batch_semi_walk(sw, nullptr);
         } else
             e = cost.affine ? nw::launch_batch_affine_walk(w, nullptr) : nw::launch_batch_walk(w, nullptr);
         if (e != hipSuccess) return NW_ERR_HIP;
@@ -631,6 +697,28 @@ int nw_align_batch_local(const int8_t *s1cat, const int64_t *off1, const int8_t 
                          int64_t *n_ops, nw_batch_stats *stats) {
     return align_batch(s1cat, off1, s2cat, off2, npairs, p, local_cost(m, gap_open), o, hits, ops, ops_off, n_ops,
                        stats);
+}
+
+int nw_score_batch_semi_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                              const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2, int64_t max_n2,
+                              const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t ends,
+                              nw_local_hit *d_hits, void *stream) {
+    return score_batch_async(c, d_s1cat, d_off1, d_s2cat, d_off2, npairs, total1, total2, max_n2, p,
+                             semi_cost(m, gap_open, ends), d_hits, stream);
+}
+
+int nw_score_batch_semi(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                        int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t ends,
+                        nw_local_hit *hits, nw_batch_stats *stats) {
+    return score_batch(s1cat, off1, s2cat, off2, npairs, p, semi_cost(m, gap_open, ends), hits, stats);
+}
+
+int nw_align_batch_semi(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                        int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t ends,
+                        const nw_batch_opts *o, nw_local_hit *hits, uint8_t *ops, const int64_t *ops_off,
+                        int64_t *n_ops, nw_batch_stats *stats) {
+    return align_batch(s1cat, off1, s2cat, off2, npairs, p, semi_cost(m, gap_open, ends), o, hits, ops, ops_off,
+                       n_ops, stats);
 }
 
 }  // extern "C"

@@ -95,6 +95,23 @@ struct BatchLocalWalkArgs {
     int32_t *hits;
 };
 
+// The semi-global kernels (nw_batch_semi.hip): the matrix launch's arguments as the
+// matrix kernels take them (the w form: m.wide and m.score as there; m.a.b.scores unused),
+// the hits in nw_local_hit's layout, and which end gaps are free (NW_ENDS_*, 0 .. 15).
+struct BatchSemiArgs {
+    BatchMatrixArgs m;
+    int32_t *hits;  // [pair][8]: score, end_i, end_j, begin_i, begin_j, 0, 0, 0
+    int32_t ends;
+};
+
+// The semi-global walk: from the hit's end cell to the begin cell, which it writes into
+// the hit: (0, 0), or where the path meets a free boundary.
+struct BatchSemiWalkArgs {
+    BatchWalkArgs w;
+    int32_t *hits;
+    int32_t ends;
+};
+
 // mapped (perm and at most kMaxPerm distinct column characters) or raw copy of s2cat
 int launch_batch_rows(const uint8_t *d_s2, int64_t total2, int32_t perm, const uint8_t *meta, uint8_t *d_rows,
                       void *stream);
@@ -115,5 +132,9 @@ int launch_batch_matrix(const BatchMatrixArgs &a, bool dirs, int grid, void *str
 // walk starts at the hit's end cell (then the reversal, as above)
 int launch_batch_local(const BatchLocalArgs &a, bool dirs, int grid, void *stream);
 int launch_batch_local_walk(const BatchLocalWalkArgs &w, void *stream);
+// semi-global alignment (free end gaps per side) with the matrix: the sweep writes a hit
+// per pair, the walk starts at the hit's end cell and stops on a free boundary or at (0, 0)
+int launch_batch_semi(const BatchSemiArgs &a, bool dirs, int grid, void *stream);
+int launch_batch_semi_walk(const BatchSemiWalkArgs &w, void *stream);
 
 }  // namespace nw

@@ -1,15 +1,17 @@
-// nw_batch_dev.h -- device code shared by the four batch kernels' files (nw_batch.hip,
-// nw_batch_affine.hip, nw_batch_matrix.hip, nw_batch_local.hip).  Private to them: every
-// file compiles its own copy (no relocatable device code), so everything here is in the
-// unnamed namespace.
+// nw_batch_dev.h -- device code shared by the five batch kernels' files (nw_batch.hip,
+// nw_batch_affine.hip, nw_batch_matrix.hip, nw_batch_local.hip, nw_batch_semi.hip).
+// Private to them: every file compiles its own copy (no relocatable device code), so
+// everything here is in the unnamed namespace.
 //
-// For all four: load_rows, uniform64, claim_ticket.  For the affine family (the last
-// three, which carry H and E from column to column and write 4 direction bits per cell):
-// the index of a cell's direction bits (NW_DIR_NIBBLE), used by both walks; and, for
-// nw_batch_matrix.hip and nw_batch_local.hip, build_profile, ProfileSub and the sweep
-// skeleton -- sweep_tickets, sweep_pair, sweep_iter -- which a file instantiates with its
-// cell policy.  The linear kernel keeps its own sweep (one value per column, 2 bits per
-// cell, no E and no F) and so does the affine kernel (nw_batch_affine.hip says why).
+// For all five: load_rows, uniform64, claim_ticket.  For the affine family (the last
+// four, which carry H and E from column to column and write 4 direction bits per cell):
+// the index of a cell's direction bits (NW_DIR_NIBBLE), used by the three walks; and, for
+// nw_batch_matrix.hip, nw_batch_local.hip and nw_batch_semi.hip, build_profile, ProfileSub
+// and the sweep skeleton -- sweep_tickets, sweep_pair, sweep_iter -- which a file
+// instantiates with its cell policy; for nw_batch_matrix.hip and nw_batch_semi.hip the
+// global cell in the w form (GlobalCell, GlobalSweep, MatrixCell).  The linear kernel
+// keeps its own sweep (one value per column, 2 bits per cell, no E and no F) and so does
+// the affine kernel (nw_batch_affine.hip says why).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -303,14 +305,112 @@ __device__ __forceinline__ void sweep_tickets(const M &mode) {
     }
 }
 
+// ---- the matrix and semi-global sweeps: the global cell in the w form ----
+
+// The global Gotoh cell in the w form (nw_batch_affine.hip's header states it; the cell,
+// its boundaries and its results are that file's affine_iter / affine_pair / ticket loop
+// in the skeleton's terms), without its substitution.
+struct GlobalCell : GotohLane {
+    int32_t go, ge;
+    int32_t *score;
+    int lane;
+
+    __device__ __forceinline__ GlobalCell(const BatchAffineArgs &AA, int32_t *out, int lane_)
+        : go(AA.gap_open), ge(AA.b.gap), score(out), lane(lane_) {}
+    __device__ __forceinline__ void row0() {
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            u[k] = go;       // H'[0][c] = go + c*ge - ge*c
+            f[k] = kNegInf;  // F'[0][c]
+        }
+        e = kNegInf;
+        dg = go;
+    }
+    // H'[r][0] = go but H'[0][0] = 0 (the diagonal of cell (1, 1)), E'[r][0] = -inf
+    __device__ __forceinline__ int32_t boundary_h(bool corner) const { return corner ? 0 : go; }
+    __device__ __forceinline__ int32_t boundary_e() const { return kNegInf; }
+    __device__ __forceinline__ int32_t opening(int32_t left) const { return left; }
+    template <int k, int SH, bool EDGE, bool DIRS>
+    __device__ __forceinline__ void cell(int32_t d, int32_t &diag, int32_t &left, int32_t &el, bool act, int32_t,
+                                         uint32_t &bits) {
+        const int32_t up = u[k];
+        const int32_t fo = up + go, eo = left + go;  // a run opened from H'
+        const int32_t fn = max(f[k], fo);
+        const int32_t en = max(el, eo);
+        // H' = max(H'_diag + s - 2 ge, F', E')
+        int32_t x = max(max(d, fn), en);
+        if constexpr (DIRS) {
+            uint32_t code = x == d ? 0u : x == fn ? 1u : 2u;
+            code |= el > eo ? 4u : 0u;
+            code |= f[k] > fo ? 8u : 0u;
+            bits |= code << SH;
+        }
+        diag = up;
+        if constexpr (EDGE) {
+            x = act ? x : up;
+            f[k] = act ? fn : f[k];
+        } else {
+            f[k] = fn;
+        }
+        u[k] = x;
+        left = x;
+        el = en;
+    }
+    __device__ __forceinline__ void group_end() {}
+    // every lane now holds row n2 of its columns
+    __device__ __forceinline__ void strip_end(bool last, int32_t cl, int32_t n1, int32_t n2) {
+        if (last) {
+#pragma unroll
+            for (int k = 0; k < C; ++k)
+                if (cl + k == n1) *score = u[k] + ge * (n2 + n1);
+        }
+    }
+    __device__ __forceinline__ void pair_end() {}
+};
+
+// What the global kernels write for a pair they do not sweep.
+struct GlobalSweep {
+    const BatchAffineArgs &AA;
+    __device__ __forceinline__ const BatchAffineArgs &affine() const { return AA; }
+    __device__ __forceinline__ int32_t *result(int pair) const { return AA.b.scores + pair; }
+    // not a pair this launch was sized for: the column scratch would not hold it
+    __device__ __forceinline__ void refused(int32_t *score, int lane) const {
+        if (lane == 0) *score = INT32_MIN;
+    }
+    // no cells: the corner of the boundary, one gap (none for 0 x 0)
+    __device__ __forceinline__ void empty(int32_t *score, int32_t n, int lane) const {
+        if (lane == 0) *score = n > 0 ? AA.gap_open + AA.b.gap * n : 0;
+    }
+};
+
+template <bool WIDE>
+struct MatrixCell : GlobalCell, ProfileSub {
+    const BatchMatrixArgs &MA;
+    int32_t bias;  // WIDE: -2 ge
+
+    template <class M>
+    __device__ __forceinline__ MatrixCell(const M &mode, int32_t *out, int lane_)
+        : GlobalCell(mode.AA, out, lane_), ProfileSub{mode.pl}, MA(mode.MA), bias(-2 * mode.AA.b.gap) {}
+    __device__ __forceinline__ void strip_begin(const uint8_t *__restrict__ s1, int32_t n1, int32_t cl) {
+        row0();
+        build(MA, s1, n1, cl);
+    }
+    template <int q, int k>
+    __device__ __forceinline__ int32_t diag_sub(int32_t diag) const {
+        int32_t d = diag + score_byte<q, k>();
+        if constexpr (WIDE) d += bias;
+        return d;
+    }
+};
+
 // ---- the affine family: the direction bits of a cell ----
 
 // NW_DIR_NIBBLE(bits, d, iters, r, c): declares `bits`, the four direction bits of cell
 // (r, c), r, c >= 1, of the block `d` of a pair whose strips have `iters` iterations.  The
 // cell was computed in strip p = (c-1) / 256 by lane l = ((c-1) % 256) / 4, column k =
 // (c-1) % 4, at step s = r + l: nibble k % 2 of byte (s % 2) * 2 + k / 2 of dword [p]
-// [s / 64][s % 64 / 4][s % 4 / 2][l].  The two walks (nw_batch_affine_walk, nw_batch_local_
-// walk) use it.  A macro, not a function: through an inlined function the walks' loops
+// [s / 64][s % 64 / 4][s % 4 / 2][l].  The three walks (nw_batch_affine_walk, nw_batch_local_
+// walk, nw_batch_semi_walk) use it.  A macro, not a function: through an inlined function the walks' loops
 // came out with another register allocation and one move displaced, and the walks are
 // held to the ISA they had when each carried this expression itself.
 #define NW_DIR_NIBBLE(bits, d, iters, r, c)                                                                            \

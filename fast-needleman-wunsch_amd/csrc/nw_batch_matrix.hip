@@ -6,10 +6,12 @@
 // on columns 4l .. 4l+3, the EDGE test, the w form of H, E and F next to -2^29, the
 // two-column scratch between strips and the 4 direction bits per cell in the same layout
 // -- so the walk is that file's launch_batch_affine_walk.  The code of all that is the
-// sweep skeleton of nw_batch_dev.h, which nw_batch_local.hip runs too.  This file adds
-// the policy: the global Gotoh cell with its boundaries and results (GlobalCell,
-// GlobalSweep), the substitution read from a column profile in LDS (ProfileSub, shared
-// with nw_batch_local.hip), and the kernel that makes the row letters.
+// sweep skeleton of nw_batch_dev.h, which nw_batch_local.hip and nw_batch_semi.hip run
+// too.  The policy is that header's as well since nw_batch_semi.hip builds on it: the
+// global Gotoh cell with its boundaries and results (GlobalCell, GlobalSweep) and the
+// substitution read from a column profile in LDS (MatrixCell over ProfileSub).  This
+// file keeps the choice of the cell's variant (MatrixSweep), the kernels and the kernel
+// that makes the row letters.
 //
 // Substitution.  The matrix and the byte -> letter index travel in the kernel arguments
 // (BatchMatrixArgs, 1.5 KiB).  The row characters are the concatenated s2 mapped through
@@ -47,102 +49,6 @@
 
 namespace nw {
 namespace {
-
-// The global Gotoh cell in the w form (nw_batch_affine.hip's header states it; the cell,
-// its boundaries and its results are that file's affine_iter / affine_pair / ticket loop
-// in the skeleton's terms), without its substitution.
-struct GlobalCell : GotohLane {
-    int32_t go, ge;
-    int32_t *score;
-    int lane;
-
-    __device__ __forceinline__ GlobalCell(const BatchAffineArgs &AA, int32_t *out, int lane_)
-        : go(AA.gap_open), ge(AA.b.gap), score(out), lane(lane_) {}
-    __device__ __forceinline__ void row0() {
-#pragma unroll
-        for (int k = 0; k < C; ++k) {
-            u[k] = go;       // H'[0][c] = go + c*ge - ge*c
-            f[k] = kNegInf;  // F'[0][c]
-        }
-        e = kNegInf;
-        dg = go;
-    }
-    // H'[r][0] = go but H'[0][0] = 0 (the diagonal of cell (1, 1)), E'[r][0] = -inf
-    __device__ __forceinline__ int32_t boundary_h(bool corner) const { return corner ? 0 : go; }
-    __device__ __forceinline__ int32_t boundary_e() const { return kNegInf; }
-    __device__ __forceinline__ int32_t opening(int32_t left) const { return left; }
-    template <int k, int SH, bool EDGE, bool DIRS>
-    __device__ __forceinline__ void cell(int32_t d, int32_t &diag, int32_t &left, int32_t &el, bool act, int32_t,
-                                         uint32_t &bits) {
-        const int32_t up = u[k];
-        const int32_t fo = up + go, eo = left + go;  // a run opened from H'
-        const int32_t fn = max(f[k], fo);
-        const int32_t en = max(el, eo);
-        // H' = max(H'_diag + s - 2 ge, F', E')
-        int32_t x = max(max(d, fn), en);
-        if constexpr (DIRS) {
-            uint32_t code = x == d ? 0u : x == fn ? 1u : 2u;
-            code |= el > eo ? 4u : 0u;
-            code |= f[k] > fo ? 8u : 0u;
-            bits |= code << SH;
-        }
-        diag = up;
-        if constexpr (EDGE) {
-            x = act ? x : up;
-            f[k] = act ? fn : f[k];
-        } else {
-            f[k] = fn;
-        }
-        u[k] = x;
-        left = x;
-        el = en;
-    }
-    __device__ __forceinline__ void group_end() {}
-    // every lane now holds row n2 of its columns
-    __device__ __forceinline__ void strip_end(bool last, int32_t cl, int32_t n1, int32_t n2) {
-        if (last) {
-#pragma unroll
-            for (int k = 0; k < C; ++k)
-                if (cl + k == n1) *score = u[k] + ge * (n2 + n1);
-        }
-    }
-    __device__ __forceinline__ void pair_end() {}
-};
-
-// What the global kernels write for a pair they do not sweep.
-struct GlobalSweep {
-    const BatchAffineArgs &AA;
-    __device__ __forceinline__ const BatchAffineArgs &affine() const { return AA; }
-    __device__ __forceinline__ int32_t *result(int pair) const { return AA.b.scores + pair; }
-    // not a pair this launch was sized for: the column scratch would not hold it
-    __device__ __forceinline__ void refused(int32_t *score, int lane) const {
-        if (lane == 0) *score = INT32_MIN;
-    }
-    // no cells: the corner of the boundary, one gap (none for 0 x 0)
-    __device__ __forceinline__ void empty(int32_t *score, int32_t n, int lane) const {
-        if (lane == 0) *score = n > 0 ? AA.gap_open + AA.b.gap * n : 0;
-    }
-};
-
-template <bool WIDE>
-struct MatrixCell : GlobalCell, ProfileSub {
-    const BatchMatrixArgs &MA;
-    int32_t bias;  // WIDE: -2 ge
-
-    template <class M>
-    __device__ __forceinline__ MatrixCell(const M &mode, int32_t *out, int lane_)
-        : GlobalCell(mode.AA, out, lane_), ProfileSub{mode.pl}, MA(mode.MA), bias(-2 * mode.AA.b.gap) {}
-    __device__ __forceinline__ void strip_begin(const uint8_t *__restrict__ s1, int32_t n1, int32_t cl) {
-        row0();
-        build(MA, s1, n1, cl);
-    }
-    template <int q, int k>
-    __device__ __forceinline__ int32_t diag_sub(int32_t diag) const {
-        int32_t d = diag + score_byte<q, k>();
-        if constexpr (WIDE) d += bias;
-        return d;
-    }
-};
 
 struct MatrixSweep : GlobalSweep {
     const BatchMatrixArgs &MA;

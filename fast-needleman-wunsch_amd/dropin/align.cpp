@@ -7,7 +7,7 @@
 //   --mem BYTES / --block-rows K: align in linear memory (nw_align_ckpt) within BYTES
 //   of device memory / in blocks of K rows (a multiple of 64); the output is the same.
 //   --score-only: no alignment, the score from the table-free sweep (nw_score).
-//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only] [--gap-open G] [--matrix FILE] [--local]
+//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only] [--gap-open G] [--matrix FILE] [--local | --ends N]
 //   LIST: a text file, one pair "A.bdna B.bdna" per line (paths relative to the
 //   list's directory unless absolute); all pairs are aligned in ONE call
 //   (nw_align_batch; --score-only: nw_score_batch).  stdout: "<ms>\n", then one
@@ -30,6 +30,12 @@
 //     "Score: <max H> begin (<i>, <j>) end (<i>, <j>)"     (cells of the table: i counts B)
 //   and, unless --score-only (which prints no begin cell), the two gapped rows of the
 //   aligned segment alone, "A: ..." and "B: ..." ('-' = gap, a non-printing byte as '?').
+//   --ends N (with --batch only, not with --local; N = 0 .. 15, the sum of 1: a skipped
+//   prefix of A is free, 2: a skipped suffix of A, 4: a prefix of B, 8: a suffix of B):
+//   semi-global alignment (nw_align_batch_semi / nw_score_batch_semi), e.g. 3: all of B
+//   inside A, 12: all of A inside B, 15: overlap.  Substitution and output are --local's:
+//   the score (it may be negative), begin and end cell and the gapped rows of the aligned
+//   part; the skipped ends are not printed.
 // Argument and missing-file errors are nw_driver's (exit 1); a device failure is
 // reported on stderr and exits 2.
 #include <chrono>
@@ -154,12 +160,15 @@ static std::string row_text(const std::vector<int8_t> &row) {
 
 // --batch LIST: every pair of the list in one call
 static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bool score_only, const int32_t *gap_open,
-                     const char *matrix, bool local) {
+                     const char *matrix, bool local, int ends) {
     nw_submat mat;
     bool listed[256];
-    if (local && matrix == nullptr) {
+    const bool semi = ends >= 0;
+    const bool hit_lines = local || semi;  // a result is an nw_local_hit
+    if (hit_lines && matrix == nullptr) {
         if (p.match < -128 || p.match > 127 || p.mismatch < -128 || p.mismatch > 127) {
-            std::cout << "error: --local without --matrix needs match and mismatch in -128..127" << std::endl;
+            std::cout << "error: " << (local ? "--local" : "--ends")
+                      << " without --matrix needs match and mismatch in -128..127" << std::endl;
             return 1;
         }
         uniform_dna(p, &mat, listed);
@@ -199,7 +208,7 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
                 std::cout << "ERROR: no such file " << path << std::endl;
                 return 1;
             }
-            if (matrix != nullptr || local)
+            if (matrix != nullptr || hit_lines)
                 for (int64_t x = 0; x < n; ++x)
                     if (!listed[(unsigned char)s[x]]) {
                         std::cout << "ERROR: byte " << (int)(unsigned char)s[x] << " of " << path
@@ -229,6 +238,12 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
                         : nw_align_batch_local(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
                                                gap_open ? *gap_open : 0, &bo, hits.data(), ops.data(), ops_off.data(),
                                                n_ops.data(), nullptr);
+    else if (semi)
+        st = score_only ? nw_score_batch_semi(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
+                                              gap_open ? *gap_open : 0, ends, hits.data(), nullptr)
+                        : nw_align_batch_semi(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
+                                              gap_open ? *gap_open : 0, ends, &bo, hits.data(), ops.data(),
+                                              ops_off.data(), n_ops.data(), nullptr);
     else if (matrix != nullptr)
         st = score_only ? nw_score_batch_matrix(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
                                                 gap_open ? *gap_open : 0, scores.data(), nullptr)
@@ -252,8 +267,8 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
         return 2;
     }
     std::cout << std::chrono::duration_cast<std::chrono::milliseconds>(wallDiff).count() << "\n";
-    for (int64_t i = 0; i < npairs && !local; ++i) std::cout << "Score: " << scores[(size_t)i] << "\n";
-    for (int64_t i = 0; i < npairs && local; ++i) {
+    for (int64_t i = 0; i < npairs && !hit_lines; ++i) std::cout << "Score: " << scores[(size_t)i] << "\n";
+    for (int64_t i = 0; i < npairs && hit_lines; ++i) {
         const nw_local_hit &h = hits[(size_t)i];
         std::cout << "Score: " << h.score;
         if (!score_only) std::cout << " begin (" << h.begin_i << ", " << h.begin_j << ")";
@@ -285,6 +300,7 @@ int main(int argc, char **argv) {
     const char *batch = nullptr, *matrix = nullptr;
     int32_t gap_open = 0;
     bool affine = false, local = false;
+    int ends = -1;  // --ends N: semi-global
     for (int a = 1; a < argc; ++a) {
         if (std::strcmp(argv[a], "--scheme") == 0) {
             int m, mm, g;
@@ -322,6 +338,15 @@ int main(int argc, char **argv) {
             matrix = argv[++a];
         } else if (std::strcmp(argv[a], "--local") == 0) {
             local = true;
+        } else if (std::strcmp(argv[a], "--ends") == 0) {
+            int v = 0;
+            char tail = 0;
+            if (a + 1 >= argc || std::sscanf(argv[a + 1], "%d%c", &v, &tail) != 1 || v < 0 || v > NW_ENDS_OVERLAP) {
+                std::cout << "error: --ends expects a number in 0..15" << std::endl;
+                return 1;
+            }
+            ends = v;
+            ++a;
         } else if (std::strcmp(argv[a], "--score-only") == 0) {
             score_only = true;
         } else if (std::strcmp(argv[a], "--batch") == 0) {
@@ -337,8 +362,12 @@ int main(int argc, char **argv) {
     if (batch != nullptr) {
         if (!pos.empty() || co.block_rows != 0) {
             std::cout << "error: --batch takes the list alone (and --scheme, --mem, --score-only, --gap-open, "
-                         "--matrix, --local)"
+                         "--matrix, --local, --ends)"
                       << std::endl;
+            return 1;
+        }
+        if (local && ends >= 0) {
+            std::cout << "error: --ends cannot be combined with --local (choose one)" << std::endl;
             return 1;
         }
         if (local) {
@@ -348,7 +377,12 @@ int main(int argc, char **argv) {
             }
             p.mode = NW_MODE_SW;
         }
-        return run_batch(batch, p, co.mem_bytes, score_only, affine ? &gap_open : nullptr, matrix, local);
+        return run_batch(batch, p, co.mem_bytes, score_only, affine ? &gap_open : nullptr, matrix, local, ends);
+    }
+    if (ends >= 0) {
+        std::cout << "error: --ends needs --batch (semi-global alignment is built for the batched alignment only)"
+                  << std::endl;
+        return 1;
     }
     if (local) {
         std::cout << "error: --local needs --batch (the one-pair local alignment is nw_sw_align's)" << std::endl;

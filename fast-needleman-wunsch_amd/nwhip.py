@@ -26,6 +26,9 @@ NW_ERR_TABLE = 7  # traceback: a cell no move reproduces (not a table of these p
 MODE_NW, MODE_SW = 0, 1  # nw_params.mode: global (the reference fills) / Smith-Waterman local
 # nw_params.kernel: auto / anti-diagonal strips (nw_fill.hip) / row-scan panels (nw_rows.hip)
 KERNEL_AUTO, KERNEL_STRIPS, KERNEL_PANELS = 0, 1, 2
+# the `ends` of the semi-global batch entries (NW_ENDS_*): which end gaps are free
+ENDS_S1_BEGIN, ENDS_S1_END, ENDS_S2_BEGIN, ENDS_S2_END = 1, 2, 4, 8
+ENDS_GLOBAL, ENDS_S2_IN_S1, ENDS_S1_IN_S2, ENDS_OVERLAP = 0, 3, 12, 15
 
 # every symbol include/nw_hip.h declares (checked by tests/test_host.py)
 EXPORTS = ["nw_params_default", "nw_strerror", "nw_version", "nw_fill", "nw_table_pitch",
@@ -44,7 +47,8 @@ EXPORTS = ["nw_params_default", "nw_strerror", "nw_version", "nw_fill", "nw_tabl
            "nw_batch_affine_dir_bytes", "nw_score_batch_affine_async", "nw_score_batch_affine",
            "nw_align_batch_affine", "nw_ops_score_affine",
            "nw_score_batch_matrix_async", "nw_score_batch_matrix", "nw_align_batch_matrix", "nw_ops_score_matrix",
-           "nw_score_batch_local_async", "nw_score_batch_local", "nw_align_batch_local"]
+           "nw_score_batch_local_async", "nw_score_batch_local", "nw_align_batch_local",
+           "nw_score_batch_semi_async", "nw_score_batch_semi", "nw_align_batch_semi"]
 IPC_HANDLE_BYTES = 64
 
 
@@ -273,6 +277,15 @@ def lib() -> ctypes.CDLL:
     L.nw_align_batch_local.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams), _smp,
                                        ctypes.c_int32, ctypes.POINTER(NwBatchOpts), _lhp, _u8p, _i64p_, _i64p_,
                                        ctypes.POINTER(NwBatchStats)]
+    L.nw_score_batch_semi_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.POINTER(NwParams), _smp, ctypes.c_int32,
+                                            ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    L.nw_score_batch_semi.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams), _smp,
+                                      ctypes.c_int32, ctypes.c_int32, _lhp, ctypes.POINTER(NwBatchStats)]
+    L.nw_align_batch_semi.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams), _smp,
+                                      ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(NwBatchOpts), _lhp, _u8p,
+                                      _i64p_, _i64p_, ctypes.POINTER(NwBatchStats)]
     L.nw_debug_tb_shift.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                     ctypes.c_int64]
     L.nw_debug_tb_shift.restype = ctypes.c_int64
@@ -835,6 +848,56 @@ def align_batch_local(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, m
                                     ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
     if st != NW_OK:
         raise NwError(st, "nw_align_batch_local")
+    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
+    return hits[:n], out, stats
+
+
+def score_batch_semi(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, ends: int = ENDS_S2_IN_S1,
+                     waves: int = 0, device: int = -1, return_stats: bool = False):
+    """Batched semi-global alignment scores (nw_score_batch_semi): Gotoh with substitution
+    by `mat` and the end gaps of `ends` (ENDS_* bits) free.  Returns a LOCAL_HIT_DTYPE array
+    as score_batch_local does: score (it may be negative), end_i, end_j (the first row-major
+    maximum among the admissible end cells) and begin_i = begin_j = -1."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    mat.check(s1, s2)
+    n = len(pairs)
+    hits = np.zeros(max(n, 1), LOCAL_HIT_DTYPE)
+    stats = NwBatchStats()
+    p = params((1, 0, int(gap)), waves, device)
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_score_batch_semi(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
+                                   off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
+                                   int(gap_open), int(ends), hits.ctypes.data_as(ctypes.POINTER(NwLocalHit)),
+                                   ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_score_batch_semi")
+    return (hits[:n], stats) if return_stats else hits[:n]
+
+
+def align_batch_semi(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, ends: int = ENDS_S2_IN_S1,
+                     mem_bytes: int = 0, waves: int = 0, device: int = -1):
+    """Batched semi-global alignments (nw_align_batch_semi): (hits, [ops of pair 0, ..],
+    NwBatchStats), as align_batch_local returns them.  A pair's ops (0 diag, 1 up, 2 left)
+    lead from its begin cell to its end cell; the skipped ends emit nothing."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    mat.check(s1, s2)
+    n = len(pairs)
+    ops_off = off1 + off2
+    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
+    hits = np.zeros(max(n, 1), LOCAL_HIT_DTYPE)
+    n_ops = np.zeros(max(n, 1), np.int64)
+    stats = NwBatchStats()
+    p = params((1, 0, int(gap)), waves, device)
+    o = NwBatchOpts(int(mem_bytes))
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_align_batch_semi(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
+                                   off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
+                                   int(gap_open), int(ends), ctypes.byref(o),
+                                   hits.ctypes.data_as(ctypes.POINTER(NwLocalHit)),
+                                   ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                   ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_align_batch_semi")
     out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
     return hits[:n], out, stats
 
@@ -1470,6 +1533,34 @@ class Context:
             ctypes.c_void_p(stream.cuda_stream))
         if st != NW_OK:
             raise NwError(st, "nw_score_batch_local_async")
+        return hits[:npairs]
+
+    def score_batch_semi(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, mat: SubMatrix, gap: int = -1,
+                         gap_open: int = 0, ends: int = ENDS_S2_IN_S1, stream=None, waves: int = 0):
+        """Semi-global alignment hits of a batch on device tensors (nw_score_batch_semi_async):
+        the arguments of Context.score_batch_local and `ends` (ENDS_* bits).  Returns an int32
+        CUDA tensor (npairs, 8) in nw_local_hit's layout: score, end_i, end_j, begin_i =
+        begin_j = -1, three zeros; a pair longer than max_n2: INT32_MIN and -1 in the four
+        coordinates.  Ordered on `stream`; nothing is synchronised."""
+        import torch
+        if mat.other is None and not mat.listed.all():
+            raise ValueError("Context.score_batch_semi needs a matrix with other= (it cannot check the sequences)")
+        npairs = int(d_off1.numel()) - 1
+        assert d_off1.dtype == torch.int64 and d_off2.dtype == torch.int64 and int(d_off2.numel()) == npairs + 1
+        assert d_off1.is_contiguous() and d_off2.is_contiguous()
+        t1, t2 = int(d_s1cat.numel()), int(d_s2cat.numel())
+        if stream is None:
+            stream = torch.cuda.current_stream(d_off1.device)
+        with torch.cuda.stream(stream):
+            hits = torch.zeros((max(npairs, 1), 8), dtype=torch.int32, device=d_off1.device)
+        p = params((1, 0, int(gap)), waves, self.device)
+        st = lib().nw_score_batch_semi_async(
+            self._h, ctypes.c_void_p(d_s1cat.data_ptr() if t1 else 0), ctypes.c_void_p(d_off1.data_ptr()),
+            ctypes.c_void_p(d_s2cat.data_ptr() if t2 else 0), ctypes.c_void_p(d_off2.data_ptr()), npairs, t1, t2,
+            int(max_n2), ctypes.byref(p), ctypes.byref(mat.c), int(gap_open), int(ends),
+            ctypes.c_void_p(hits.data_ptr()), ctypes.c_void_p(stream.cuda_stream))
+        if st != NW_OK:
+            raise NwError(st, "nw_score_batch_semi_async")
         return hits[:npairs]
 
     def traceback_block(self, d_s1, d_s2_block, table, row0: int, scheme=(1, 0, -1), stream=None, band: int = 0,

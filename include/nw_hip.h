@@ -594,7 +594,7 @@ int nw_align_batch_matrix(const int8_t *s1cat, const int64_t *off1, const int8_t
  * the sweep writes the hit, the walk reads its start from it on the device (kernels:
  * csrc/nw_batch_local.hip). */
 typedef struct nw_local_hit {      /* 32 bytes */
-    int32_t score;                 /* max H, >= 0                                    */
+    int32_t score;                 /* max H, >= 0 (semi-global entries: may be < 0)  */
     int32_t end_i, end_j;          /* first row-major maximum; (0,0) when score == 0 */
     int32_t begin_i, begin_j;      /* align entry: where the walk stopped; score entries: -1 */
     int32_t reserved[3];           /* written as 0 */
@@ -613,6 +613,71 @@ int nw_align_batch_local(const int8_t *s1cat, const int64_t *off1, const int8_t 
                          int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open,
                          const nw_batch_opts *o, nw_local_hit *hits, uint8_t *ops, const int64_t *ops_off,
                          int64_t *n_ops, nw_batch_stats *stats);
+
+/* Batched SEMI-GLOBAL alignment: free end gaps per side ---------------------------
+ * Between the matrix entries (both sequences end to end) and the local ones (the best
+ * pair of substrings): a read that must align over its whole length somewhere inside a
+ * reference window ("fit"), a primer inside a read, two reads that dovetail.  `ends` is
+ * a set of four bits; s1 runs along the columns and s2 along the rows, as everywhere:
+ *   NW_ENDS_S1_BEGIN (1)  a skipped prefix of s1 costs nothing: H[0][j] = 0
+ *   NW_ENDS_S1_END   (2)  a skipped suffix of s1 costs nothing: the end cell may be any (n2, j)
+ *   NW_ENDS_S2_BEGIN (4)  H[i][0] = 0
+ *   NW_ENDS_S2_END   (8)  the end cell may be any (i, n1)
+ * NW_ENDS_GLOBAL = 0, NW_ENDS_S2_IN_S1 = 3 (all of s2 inside s1), NW_ENDS_S1_IN_S2 = 12,
+ * NW_ENDS_OVERLAP = 15; the dovetails are 9 (a suffix of s1 against a prefix of s2) and 6.
+ * A path runs from a begin cell -- (0, 0), or any (0, j) with bit 1, or any (i, 0) with
+ * bit 4 -- to an end cell -- (n2, n1), or any (n2, j), 0 <= j <= n1, with bit 2, or any
+ * (i, n1), 0 <= i <= n2, with bit 8 --, and the score is the best Gotoh score of such a
+ * path; it may be negative.  As a table: the matrix entries' recurrence, no floor,
+ *   E, F and H of inner cells as there;  E[i][0] = F[0][j] = -inf;  H[0][0] = 0;
+ *   a boundary that is not free holds go + k * ge, a free one 0.
+ * End cell: among the admissible end cells of maximal H the first in row-major order
+ * (smallest i, then smallest j), the local entries' rule; (n2, 0) and (0, n1) are
+ * candidates where their side is free, so with ends = 15 the score is >= 0.
+ * Walk: the affine entries' machine of three states, started at the end cell in state H.
+ * At (0, 0) it stops; on row 0 it stops if bit 1 is set, else it goes left to (0, 0)
+ * emitting lefts; on column 0 it stops if bit 4 is set, else it goes up emitting ups; the
+ * cell where it stops is the begin cell.  Tie-breaks are the affine entries': diag, then
+ * F, then E; opening wins over extending.  Ops run begin -> end, n_ops <= n1 + n2, and
+ * nw_ops_score_matrix(..., begin_i, begin_j, ...) of them equals the score; the skipped
+ * prefix and suffix emit nothing.
+ * The result is an nw_local_hit whose score may be negative here.  The score entries
+ * write -1 into the begin cell.  In the _async form a pair longer than max_n2 gets
+ * INT32_MIN and -1 in the four coordinates, and the kernel answers pairs with an empty
+ * side; in the host forms the host answers them without a launch, ops included (a table
+ * with an empty side follows the same definition: one boundary, no special rule).
+ * ends = 0: score, ops and n_ops are byte for byte nw_*_batch_matrix's, end (n2, n1),
+ * begin (0, 0).  Parameters, refusals and their order are the matrix entries'
+ * (NW_MODE_NW, gap_open <= 0, the matrix checks); then ends outside 0 .. 15 is
+ * NW_ERR_ARG, before the range bound, which is the matrix entries' unchanged:
+ *   3*|gap_open| + (M + |gap|) * (n1 + n2 + 2) < 2^28
+ * Direction bytes (nw_batch_affine_dir_bytes), chunking by mem_bytes, NW_ERR_OOM, slot
+ * sizes, longest-first tickets and the statistics are the matrix entries' too (kernels:
+ * csrc/nw_batch_semi.hip). */
+enum {
+    NW_ENDS_S1_BEGIN = 1,
+    NW_ENDS_S1_END = 2,
+    NW_ENDS_S2_BEGIN = 4,
+    NW_ENDS_S2_END = 8,
+    NW_ENDS_GLOBAL = 0,
+    NW_ENDS_S2_IN_S1 = 3,
+    NW_ENDS_S1_IN_S2 = 12,
+    NW_ENDS_OVERLAP = 15
+};
+
+int nw_score_batch_semi_async(nw_ctx *ctx, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                              const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2, int64_t max_n2,
+                              const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t ends,
+                              nw_local_hit *d_hits, void *stream);
+
+int nw_score_batch_semi(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                        int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t ends,
+                        nw_local_hit *hits, nw_batch_stats *stats);
+
+int nw_align_batch_semi(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                        int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t ends,
+                        const nw_batch_opts *o, nw_local_hit *hits, uint8_t *ops, const int64_t *ops_off,
+                        int64_t *n_ops, nw_batch_stats *stats);
 
 /* Launch-only variant for timing loops: no synchronisation, no readback. */
 int nw_fill_device_async(nw_ctx *ctx, const int8_t *d_s1, int64_t n1,

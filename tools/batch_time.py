@@ -32,6 +32,13 @@ library's one-pair path, unchanged by the batch; its scores must equal the batch
                     same process the global matrix entries on the SAME pairs and matrix (the
                     yardstick) and the ratios.  Writes profiles/batch_local_time.json.
 
+  --ends N [N ..]   the semi-global entries (nw_score_batch_semi, nw_align_batch_semi) with each of
+                    these `ends` (3: all of s2 inside s1, 15: overlap, ..) on pairs over --matrix's
+                    20-letter alphabet and matrix, gap -1 and --gap-open (default -11); every pair
+                    holds a planted fit (--local's planted segments).  In the same process, before
+                    them, the global matrix entries on the SAME pairs and matrix (the yardstick)
+                    and the ratios.  Writes profiles/batch_semi_time.json.
+
 The score kernel's yardstick is the checkpoint sweep's pace on one huge table
 (profiles/ckpt_time.json: 262144^2 in 20.62 ms); `fraction_of_sweep_pace` states it.
 """
@@ -60,14 +67,16 @@ ap.add_argument("--loop-reps", type=int, default=5)
 ap.add_argument("--gap-open", type=int, default=None)
 ap.add_argument("--matrix", type=int, default=None, nargs="?", const=20)
 ap.add_argument("--local", action="store_true")
+ap.add_argument("--ends", type=int, default=None, nargs="+")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
-if args.local:
+if args.local or args.ends is not None:
     args.matrix = 20
 if args.matrix is not None and args.gap_open is None:
     args.gap_open = -11
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "batch_local_time.json" if args.local else
+    args.out = os.path.join(ROOT, "profiles", "batch_semi_time.json" if args.ends is not None else
+                            "batch_local_time.json" if args.local else
                             "batch_matrix_time.json" if args.matrix is not None else
                             "batch_time.json" if args.gap_open is None else "batch_affine_time.json")
 scheme = (1, 0, -1)
@@ -226,6 +235,30 @@ def run_local(name):
     return e
 
 
+def run_semi(name):
+    go, ge = args.gap_open, -1
+    letters, mat = make_matrix(20)
+    pairs = plant_segments(make_pairs(name, letters), letters, 7 + len(name))
+    cells = sum(a.size * b.size for a, b in pairs)
+    e = {"shape": name, "pairs": len(pairs), "cells": int(cells), "gap_open": go, "gap": ge, "letters": 20,
+         "matrix_entries": [int(mat.scores.min()), int(mat.scores.max())],
+         "lengths": "uniform %d..%d" % SHAPES[name][1:] if name == "mixed" else "%d x %d" % SHAPES[name][1:]}
+    gs, ga, glob = time_entries(pairs, cells, lambda p, **kw: nwhip.score_batch_matrix(p, mat, ge, go, **kw),
+                                lambda p: nwhip.align_batch_matrix(p, mat, ge, go))
+    e["score_batch_matrix"], e["align_batch_matrix"] = gs, ga
+    e["median_global_score"] = int(np.median(glob))
+    for ends in args.ends:
+        s, a, hits = time_entries(pairs, cells, lambda p, **kw: nwhip.score_batch_semi(p, mat, ge, go, ends, **kw),
+                                  lambda p: nwhip.align_batch_semi(p, mat, ge, go, ends), key=lambda h: h["score"])
+        e["ends_%d" % ends] = {
+            "median_score": int(np.median(hits["score"])), "score_batch_semi": s, "align_batch_semi": a,
+            "score_semi_over_matrix": round(s["fill_ms"] / gs["fill_ms"], 3),
+            "align_fill_semi_over_matrix": round(a["fill_ms"] / ga["fill_ms"], 3),
+            "align_fill_walk_semi_over_matrix": round(a["fill_walk_ms"] / ga["fill_walk_ms"], 3)}
+    print(json.dumps(e), flush=True)
+    return e
+
+
 def run(name):
     pairs = make_pairs(name)
     cells = sum(a.size * b.size for a, b in pairs)
@@ -270,7 +303,7 @@ if os.path.exists(args.out):
 rec.update({"device": torch.cuda.get_device_name(0), "library": nwhip.version(), "scheme": list(scheme),
             "reps": args.reps, "sweep_yardstick_gcups": round(SWEEP_GCUPS, 1)})
 for name in (list(SHAPES) if args.shape == "all" else [args.shape]):
-    rec["shapes"][name] = (run_local(name) if args.local else run_matrix(name) if args.matrix is not None else
+    rec["shapes"][name] = (run_semi(name) if args.ends is not None else run_local(name) if args.local else run_matrix(name) if args.matrix is not None else
                            run(name) if args.gap_open is None else run_affine(name))
 os.makedirs(os.path.dirname(args.out), exist_ok=True)
 with open(args.out, "w") as f:
