@@ -16,7 +16,10 @@
 // entries (nw_score_batch_semi_async, nw_score_batch_semi, nw_align_batch_semi; kernels in
 // nw_batch_semi.hip) are the matrix ones with an `ends` set: mode, matrix bytes, range and
 // refusals as there, hits as the result like the local ones, and empty pairs answered here
-// from the definition.
+// from the definition.  The banded entries (nw_score_batch_banded_async, nw_score_batch_
+// banded, nw_align_batch_banded; kernels in nw_batch_banded.hip) are the matrix ones with a
+// band width: the Cost carries it, a pair's direction bytes are nw_batch_banded_dir_bytes,
+// and the sweep and the walk are that file's.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -41,10 +44,13 @@ struct Cost {
     bool local = false;   // Smith-Waterman (matrix is then true): a result is an nw_local_hit
     bool semi = false;    // free end gaps per side (matrix is then true): a result is an nw_local_hit
     int32_t ends = 0;     // semi: NW_ENDS_* bits
+    bool banded = false;  // cells within `band` diagonals only (matrix is then true)
+    int32_t band = 0;
     bool hits() const { return local || semi; }
     size_t out_bytes() const { return hits() ? sizeof(nw_local_hit) : sizeof(int32_t); }
     int64_t col_words(int64_t max_n2) const { return nw::batch_col_words(max_n2) * (affine ? 2 : 1); }
     int64_t dir_bytes(int64_t n1, int64_t n2) const {
+        if (banded) return nw_batch_banded_dir_bytes(n1, n2, band);
         return affine ? nw_batch_affine_dir_bytes(n1, n2) : nw_batch_dir_bytes(n1, n2);
     }
     // a pair without cells: one run along the boundary
@@ -88,6 +94,13 @@ Cost semi_cost(const nw_submat *m, int32_t gap_open, int32_t ends) {
     Cost c = matrix_cost(m, gap_open);
     c.semi = true;
     c.ends = ends;
+    return c;
+}
+
+Cost banded_cost(const nw_submat *m, int32_t gap_open, int32_t band) {
+    Cost c = matrix_cost(m, gap_open);
+    c.banded = true;
+    c.band = band;
     return c;
 }
 
@@ -165,6 +178,7 @@ int params_check(const nw_params *p, int64_t npairs, const Cost &cost) {
     if (npairs < 0 || npairs >= INT32_MAX) return NW_ERR_ARG;
     if (cost.matrix && !valid_submat(cost.mat)) return NW_ERR_ARG;
     if (cost.semi && (cost.ends < 0 || cost.ends > NW_ENDS_OVERLAP)) return NW_ERR_ARG;
+    if (cost.banded && cost.band < 0) return NW_ERR_ARG;
     return NW_OK;
 }
 
@@ -277,6 +291,11 @@ int batch_run(nw_ctx *c, const nw::BatchMatrixArgs &ma, const Cost &cost, bool d
         sa.m.a.b.scores = nullptr;
         sa.ends = cost.ends;
         e = nw::launch_batch_semi(sa, dirs, g, stream);
+    } else if (cost.banded) {
+        nw::BatchBandedArgs ba;
+        ba.m = ma;
+        ba.band = cost.band;
+        e = nw::launch_batch_banded(ba, dirs, g, stream);
     } else
         e = cost.matrix ? nw::launch_batch_matrix(ma, dirs, g, stream)
             : cost.affine ? nw::launch_batch_affine(aa, dirs, g, stream)
@@ -565,6 +584,11 @@ int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
             sw.hits = d.scores;
             sw.ends = cost.ends;
             e = nw::launch_batch_semi_walk(sw, nullptr);
+        } else if (cost.banded) {  // the affine walk over the strips' ranges
+            nw::BatchBandedWalkArgs bw;
+            bw.w = w;
+            bw.band = cost.band;
+            e = nw::launch_batch_banded_walk(bw, nullptr);
         } else
             e = cost.affine ? nw::launch_batch_affine_walk(w, nullptr) : nw::launch_batch_walk(w, nullptr);
         if (e != hipSuccess) return NW_ERR_HIP;
@@ -613,6 +637,12 @@ int64_t nw_batch_dir_bytes(int64_t n1, int64_t n2) {
 int64_t nw_batch_affine_dir_bytes(int64_t n1, int64_t n2) {
     const int64_t b = nw_batch_dir_bytes(n1, n2);
     return b < 0 ? b : 2 * b;
+}
+
+int64_t nw_batch_banded_dir_bytes(int64_t n1, int64_t n2, int32_t band) {
+    if (n1 < 0 || n2 < 0 || band < 0) return -1;
+    if (n1 == 0 || n2 == 0) return 0;
+    return nw::batch_strips(n1) * nw::batch_banded_slots(n1, n2, band) * 2 * nw::kBatchDirIter;
 }
 
 int nw_score_batch_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
@@ -718,6 +748,28 @@ int nw_align_batch_semi(const int8_t *s1cat, const int64_t *off1, const int8_t *
                         const nw_batch_opts *o, nw_local_hit *hits, uint8_t *ops, const int64_t *ops_off,
                         int64_t *n_ops, nw_batch_stats *stats) {
     return align_batch(s1cat, off1, s2cat, off2, npairs, p, semi_cost(m, gap_open, ends), o, hits, ops, ops_off,
+                       n_ops, stats);
+}
+
+int nw_score_batch_banded_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                                const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2,
+                                int64_t max_n2, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                                int32_t band, int32_t *d_scores, void *stream) {
+    return score_batch_async(c, d_s1cat, d_off1, d_s2cat, d_off2, npairs, total1, total2, max_n2, p,
+                             banded_cost(m, gap_open, band), d_scores, stream);
+}
+
+int nw_score_batch_banded(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                          int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t band,
+                          int32_t *scores, nw_batch_stats *stats) {
+    return score_batch(s1cat, off1, s2cat, off2, npairs, p, banded_cost(m, gap_open, band), scores, stats);
+}
+
+int nw_align_batch_banded(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                          int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t band,
+                          const nw_batch_opts *o, int32_t *scores, uint8_t *ops, const int64_t *ops_off,
+                          int64_t *n_ops, nw_batch_stats *stats) {
+    return align_batch(s1cat, off1, s2cat, off2, npairs, p, banded_cost(m, gap_open, band), o, scores, ops, ops_off,
                        n_ops, stats);
 }
 

@@ -112,6 +112,52 @@ struct BatchSemiWalkArgs {
     int32_t ends;
 };
 
+// The banded kernels (nw_batch_banded.hip): the matrix launch's arguments and the band
+// width w >= 0 of the call (include/nw_hip.h: cell (i, j) is in the band iff dlo <= i - j
+// <= dhi, dlo = min(0, n2 - n1) - w, dhi = max(0, n2 - n1) + w).
+struct BatchBandedArgs {
+    BatchMatrixArgs m;
+    int32_t band;
+};
+
+// The banded walk: the affine walk over direction blocks that hold only the iterations of
+// each strip's range.
+struct BatchBandedWalkArgs {
+    BatchWalkArgs w;
+    int32_t band;
+};
+
+// The geometry of a banded pair, shared by the sweep, the walk and the host's sizes.
+// dlo and dhi are kept within kBandedPad diagonals of the table's own (-n1 .. n2): the
+// cells in the band are the same, and every sum below stays in int32 for the pairs the
+// range bound admits.  A strip of 256 columns starting at column 256p + 1 has in-band
+// cells at steps 256p + 1 + dlo .. 256p + 319 + dhi (rows 256p + 1 + dlo .. 256p + 256 +
+// dhi, and lane l computes row r at step r + l); it runs the iterations
+//     first(p) = max(0, floor((256p + dlo) / 64))   (one step earlier: the diagonal of the
+//                                                     first in-band cell comes in as a feed)
+//     .. min(iters - 1, floor((256p + 319 + dhi) / 64) + 1)   (the right column's last
+//                                                     block is stored one iteration later)
+// which are at most ceil((dhi - dlo + 319) / 64) + 2 -- the slots of a strip in the pair's
+// direction block, never more than the unbanded batch_iters(n2).
+constexpr int64_t kBandedPad = 1024;
+constexpr int64_t batch_banded_dlo(int64_t n1, int64_t n2, int64_t band) {
+    const int64_t d = (n2 < n1 ? n2 - n1 : 0) - band;
+    return d < -n1 - kBandedPad ? -n1 - kBandedPad : d;
+}
+constexpr int64_t batch_banded_dhi(int64_t n1, int64_t n2, int64_t band) {
+    const int64_t d = (n2 > n1 ? n2 - n1 : 0) + band;
+    return d > n2 + kBandedPad ? n2 + kBandedPad : d;
+}
+constexpr int64_t batch_banded_slots(int64_t n1, int64_t n2, int64_t band) {
+    const int64_t span = batch_banded_dhi(n1, n2, band) - batch_banded_dlo(n1, n2, band);
+    const int64_t k = (span + 319 + 63) / 64 + 2;
+    return k < batch_iters(n2) ? k : batch_iters(n2);
+}
+constexpr int64_t batch_banded_first(int64_t p, int64_t dlo) {
+    const int64_t s = 256 * p + dlo;
+    return s > 0 ? s >> 6 : 0;
+}
+
 // mapped (perm and at most kMaxPerm distinct column characters) or raw copy of s2cat
 int launch_batch_rows(const uint8_t *d_s2, int64_t total2, int32_t perm, const uint8_t *meta, uint8_t *d_rows,
                       void *stream);
@@ -136,5 +182,9 @@ int launch_batch_local_walk(const BatchLocalWalkArgs &w, void *stream);
 // per pair, the walk starts at the hit's end cell and stops on a free boundary or at (0, 0)
 int launch_batch_semi(const BatchSemiArgs &a, bool dirs, int grid, void *stream);
 int launch_batch_semi_walk(const BatchSemiWalkArgs &w, void *stream);
+// banded global alignment with the matrix: the sweep runs each strip's iteration range
+// only, the walk indexes the direction blocks that range leaves
+int launch_batch_banded(const BatchBandedArgs &a, bool dirs, int grid, void *stream);
+int launch_batch_banded_walk(const BatchBandedWalkArgs &w, void *stream);
 
 }  // namespace nw

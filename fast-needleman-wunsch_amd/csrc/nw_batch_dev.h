@@ -1,9 +1,10 @@
-// nw_batch_dev.h -- device code shared by the five batch kernels' files (nw_batch.hip,
-// nw_batch_affine.hip, nw_batch_matrix.hip, nw_batch_local.hip, nw_batch_semi.hip).
+// nw_batch_dev.h -- device code shared by the batch kernels' files (nw_batch.hip,
+// nw_batch_affine.hip, nw_batch_matrix.hip, nw_batch_local.hip, nw_batch_semi.hip and
+// nw_batch_banded.hip, which runs sweep_tickets and sweep_iter under its own pair loop).
 // Private to them: every file compiles its own copy (no relocatable device code), so
 // everything here is in the unnamed namespace.
 //
-// For all five: load_rows, uniform64, claim_ticket.  For the affine family (the last
+// For all of them: load_rows, uniform64, claim_ticket.  For the affine family (the last
 // four, which carry H and E from column to column and write 4 direction bits per cell):
 // the index of a cell's direction bits (NW_DIR_NIBBLE), used by the three walks; and, for
 // nw_batch_matrix.hip, nw_batch_local.hip and nw_batch_semi.hip, build_profile, ProfileSub

@@ -7,7 +7,7 @@
 //   --mem BYTES / --block-rows K: align in linear memory (nw_align_ckpt) within BYTES
 //   of device memory / in blocks of K rows (a multiple of 64); the output is the same.
 //   --score-only: no alignment, the score from the table-free sweep (nw_score).
-//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only] [--gap-open G] [--matrix FILE] [--local | --ends N]
+//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only] [--gap-open G] [--matrix FILE] [--local | --ends N | --band W]
 //   LIST: a text file, one pair "A.bdna B.bdna" per line (paths relative to the
 //   list's directory unless absolute); all pairs are aligned in ONE call
 //   (nw_align_batch; --score-only: nw_score_batch).  stdout: "<ms>\n", then one
@@ -36,9 +36,14 @@
 //   inside A, 12: all of A inside B, 15: overlap.  Substitution and output are --local's:
 //   the score (it may be negative), begin and end cell and the gapped rows of the aligned
 //   part; the skipped ends are not printed.
+//   --band W (with --batch only, not with --local or --ends; W >= 0): banded global
+//   alignment (nw_align_batch_banded / nw_score_batch_banded): only paths that stay within
+//   W diagonals of the pair's own (of 0 .. |B| - |A|) count.  Substitution as --local's
+//   (--matrix, or --scheme's match / mismatch over A, C, G, T); one "Score:" line per pair.
 // Argument and missing-file errors are nw_driver's (exit 1); a device failure is
 // reported on stderr and exits 2.
 #include <chrono>
+#include <cstdint>
 #include <fstream>
 #include <sstream>
 #include <cstdio>
@@ -160,14 +165,15 @@ static std::string row_text(const std::vector<int8_t> &row) {
 
 // --batch LIST: every pair of the list in one call
 static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bool score_only, const int32_t *gap_open,
-                     const char *matrix, bool local, int ends) {
+                     const char *matrix, bool local, int ends, int64_t band) {
     nw_submat mat;
     bool listed[256];
     const bool semi = ends >= 0;
+    const bool banded = band >= 0;
     const bool hit_lines = local || semi;  // a result is an nw_local_hit
-    if (hit_lines && matrix == nullptr) {
+    if ((hit_lines || banded) && matrix == nullptr) {
         if (p.match < -128 || p.match > 127 || p.mismatch < -128 || p.mismatch > 127) {
-            std::cout << "error: " << (local ? "--local" : "--ends")
+            std::cout << "error: " << (local ? "--local" : semi ? "--ends" : "--band")
                       << " without --matrix needs match and mismatch in -128..127" << std::endl;
             return 1;
         }
@@ -208,7 +214,7 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
                 std::cout << "ERROR: no such file " << path << std::endl;
                 return 1;
             }
-            if (matrix != nullptr || hit_lines)
+            if (matrix != nullptr || hit_lines || banded)
                 for (int64_t x = 0; x < n; ++x)
                     if (!listed[(unsigned char)s[x]]) {
                         std::cout << "ERROR: byte " << (int)(unsigned char)s[x] << " of " << path
@@ -244,6 +250,12 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
                         : nw_align_batch_semi(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
                                               gap_open ? *gap_open : 0, ends, &bo, hits.data(), ops.data(),
                                               ops_off.data(), n_ops.data(), nullptr);
+    else if (banded)
+        st = score_only ? nw_score_batch_banded(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
+                                                gap_open ? *gap_open : 0, (int32_t)band, scores.data(), nullptr)
+                        : nw_align_batch_banded(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
+                                                gap_open ? *gap_open : 0, (int32_t)band, &bo, scores.data(),
+                                                ops.data(), ops_off.data(), n_ops.data(), nullptr);
     else if (matrix != nullptr)
         st = score_only ? nw_score_batch_matrix(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
                                                 gap_open ? *gap_open : 0, scores.data(), nullptr)
@@ -301,6 +313,7 @@ int main(int argc, char **argv) {
     int32_t gap_open = 0;
     bool affine = false, local = false;
     int ends = -1;  // --ends N: semi-global
+    long long band = -1;  // --band W: banded global
     for (int a = 1; a < argc; ++a) {
         if (std::strcmp(argv[a], "--scheme") == 0) {
             int m, mm, g;
@@ -347,6 +360,15 @@ int main(int argc, char **argv) {
             }
             ends = v;
             ++a;
+        } else if (std::strcmp(argv[a], "--band") == 0) {
+            long long v = 0;
+            char tail = 0;
+            if (a + 1 >= argc || std::sscanf(argv[a + 1], "%lld%c", &v, &tail) != 1 || v < 0 || v > INT32_MAX) {
+                std::cout << "error: --band expects a number >= 0 (below 2^31)" << std::endl;
+                return 1;
+            }
+            band = v;
+            ++a;
         } else if (std::strcmp(argv[a], "--score-only") == 0) {
             score_only = true;
         } else if (std::strcmp(argv[a], "--batch") == 0) {
@@ -362,12 +384,17 @@ int main(int argc, char **argv) {
     if (batch != nullptr) {
         if (!pos.empty() || co.block_rows != 0) {
             std::cout << "error: --batch takes the list alone (and --scheme, --mem, --score-only, --gap-open, "
-                         "--matrix, --local, --ends)"
+                         "--matrix, --local, --ends, --band)"
                       << std::endl;
             return 1;
         }
         if (local && ends >= 0) {
             std::cout << "error: --ends cannot be combined with --local (choose one)" << std::endl;
+            return 1;
+        }
+        if (band >= 0 && (local || ends >= 0)) {
+            std::cout << "error: --band cannot be combined with " << (local ? "--local" : "--ends")
+                      << " (the band is built for the global alignment only)" << std::endl;
             return 1;
         }
         if (local) {
@@ -377,7 +404,11 @@ int main(int argc, char **argv) {
             }
             p.mode = NW_MODE_SW;
         }
-        return run_batch(batch, p, co.mem_bytes, score_only, affine ? &gap_open : nullptr, matrix, local, ends);
+        return run_batch(batch, p, co.mem_bytes, score_only, affine ? &gap_open : nullptr, matrix, local, ends, band);
+    }
+    if (band >= 0) {
+        std::cout << "error: --band needs --batch (the band is built for the batched alignment only)" << std::endl;
+        return 1;
     }
     if (ends >= 0) {
         std::cout << "error: --ends needs --batch (semi-global alignment is built for the batched alignment only)"

@@ -679,6 +679,70 @@ int nw_align_batch_semi(const int8_t *s1cat, const int64_t *off1, const int8_t *
                         const nw_batch_opts *o, nw_local_hit *hits, uint8_t *ops, const int64_t *ops_off,
                         int64_t *n_ops, nw_batch_stats *stats);
 
+/* Batched BANDED global alignment: the matrix entries inside a band of diagonals ----
+ * For pairs whose path stays near the diagonal (reads against a window, amplicons,
+ * homologous proteins, overlaps verified after seeding): the sweep visits the band's
+ * neighbourhood only and keeps direction bits for it only.  The entries are the matrix
+ * entries' with `int32_t band` after gap_open.
+ * Definition.  band = w >= 0, one value per call.  For a pair with n1 columns (s1) and n2
+ * rows (s2) let delta = n2 - n1, dlo = min(0, delta) - w and dhi = max(0, delta) + w.
+ *   Cell (i, j), 0 <= i <= n2, 0 <= j <= n1, is IN THE BAND iff dlo <= i - j <= dhi;
+ *   boundary cells are included in this rule.
+ *   H, E and F of a cell outside the band are -inf.
+ *   Inside the band the recurrence, the boundaries (go + k * ge, H[0][0] = 0, E[i][0] =
+ *   F[0][j] = -inf), the three-state walk and its tie-breaks are the matrix entries', word
+ *   for word.
+ *   score = H[n2][n1].
+ * Equivalently: the score is the best Gotoh score over the paths (0, 0) -> (n2, n1) all of
+ * whose vertices are in the band.  Three consequences:
+ *   Every in-band inner cell has a finite H: its diagonal predecessor lies on the same
+ *   diagonal, and the path "diagonal, then one run" is always inside the band.  So the
+ *   score is always a real score; there is no sentinel.
+ *   When dlo <= -n1 and dhi >= n2 the band is the whole table -- any w >= max(n1, n2)
+ *   guarantees it -- and scores, ops and n_ops are byte for byte nw_*_batch_matrix's.
+ *   The walk never leaves the band: the predecessor it picks equals a finite H.
+ * Results are int32 scores.  The CSR layout, options, statistics, slot sizes (n1 + n2),
+ * longest-first tickets, empty-side pairs and the INT32_MIN of a pair over max_n2 in the
+ * _async form are the matrix entries'; an empty-side pair follows the definition: its one
+ * boundary is inside the band because the band widens by |delta|.  Refusals and their
+ * order are the matrix entries'; after the matrix checks and before the range bound, band
+ * < 0 is NW_ERR_ARG.  The range bound is the matrix entries' unchanged,
+ *   3*|gap_open| + (M + |gap|) * (n1 + n2 + 2) < 2^28
+ * and still holds with cells forced to -inf: its lower bound on H is the score of a path
+ * with one run up and one run left, and for an in-band cell the path "diagonal, then one
+ * run" is such a path inside the band; its upper bound does not depend on the path.  A
+ * forced -2^29 is copied, never accumulated: what is added to it (go, s - 2 ge) is added
+ * once, and the sum is dropped by the next maximum or forced again (kernels:
+ * csrc/nw_batch_banded.hip).
+ *
+ * nw_batch_banded_dir_bytes: direction bytes of one pair in nw_align_batch_banded, the
+ * number the chunking uses.  0 when a side is empty, -1 for a negative size or a negative
+ * band.  Host only.  A strip of 256 columns keeps only the 64-step iterations that can
+ * touch an in-band row of its columns:
+ *   ceil(n1 / 256) * min(n2 / 64 + 2, ceil((dhi' - dlo' + 319) / 64) + 2) * 8192
+ * with dlo' = max(dlo, -n1 - 1024), dhi' = min(dhi, n2 + 1024).  It equals
+ * nw_batch_affine_dir_bytes(n1, n2) when the band covers the table, is never above it,
+ * does not decrease when w grows, and is at most
+ *   ceil(n1 / 256) * (ceil((2 * band + |n2 - n1| + 319) / 64) + 3) * 8192
+ * (a strip's 256 columns need 256 + dhi - dlo rows; the lane skew adds 63 steps; a step
+ * range touches one more 64-step iteration than its length; the right column's last
+ * block is stored one iteration later; one row of slack covers the feed). */
+int64_t nw_batch_banded_dir_bytes(int64_t n1, int64_t n2, int32_t band);
+
+int nw_score_batch_banded_async(nw_ctx *ctx, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                                const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2,
+                                int64_t max_n2, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                                int32_t band, int32_t *d_scores, void *stream);
+
+int nw_score_batch_banded(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                          int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t band,
+                          int32_t *scores, nw_batch_stats *stats);
+
+int nw_align_batch_banded(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                          int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t band,
+                          const nw_batch_opts *o, int32_t *scores, uint8_t *ops, const int64_t *ops_off,
+                          int64_t *n_ops, nw_batch_stats *stats);
+
 /* Launch-only variant for timing loops: no synchronisation, no readback. */
 int nw_fill_device_async(nw_ctx *ctx, const int8_t *d_s1, int64_t n1,
                          const int8_t *d_s2, int64_t n2, const nw_params *p,

@@ -39,6 +39,14 @@ library's one-pair path, unchanged by the batch; its scores must equal the batch
                     them, the global matrix entries on the SAME pairs and matrix (the yardstick)
                     and the ratios.  Writes profiles/batch_semi_time.json.
 
+  --band W [W ..]   the banded entries (nw_score_batch_banded, nw_align_batch_banded) with each of these
+                    band widths (a width of 1000000 covers every table here) on --matrix's pairs and
+                    matrix, gap -1 and --gap-open (default -11).  In the same process, before them,
+                    the global matrix entries on the SAME pairs and matrix (the yardstick: code the
+                    band does not touch) and the ratios, each next to the ratio predicted from the
+                    iterations a strip sweeps (predict_band).  Writes
+                    profiles/batch_banded_time.json.
+
 The score kernel's yardstick is the checkpoint sweep's pace on one huge table
 (profiles/ckpt_time.json: 262144^2 in 20.62 ms); `fraction_of_sweep_pace` states it.
 """
@@ -68,14 +76,16 @@ ap.add_argument("--gap-open", type=int, default=None)
 ap.add_argument("--matrix", type=int, default=None, nargs="?", const=20)
 ap.add_argument("--local", action="store_true")
 ap.add_argument("--ends", type=int, default=None, nargs="+")
+ap.add_argument("--band", type=int, default=None, nargs="+")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
-if args.local or args.ends is not None:
+if args.local or args.ends is not None or args.band is not None:
     args.matrix = 20
 if args.matrix is not None and args.gap_open is None:
     args.gap_open = -11
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "batch_semi_time.json" if args.ends is not None else
+    args.out = os.path.join(ROOT, "profiles", "batch_banded_time.json" if args.band is not None else
+                            "batch_semi_time.json" if args.ends is not None else
                             "batch_local_time.json" if args.local else
                             "batch_matrix_time.json" if args.matrix is not None else
                             "batch_time.json" if args.gap_open is None else "batch_affine_time.json")
@@ -259,6 +269,67 @@ def run_semi(name):
     return e
 
 
+# VALU instructions of the masked 64-step iteration over the matrix kernel's, from the ISA of
+# the two score kernels
+MASKED_OVER_PLAIN = 1.12
+
+
+def band_iterations(n1, n2, w):
+    """(masked, plain, all): the 64-step iterations the banded sweep runs with and without the
+    mask, and those the matrix sweep runs, summed over the pair's strips (the geometry of
+    csrc/nw_batch.h batch_banded_* and csrc/nw_batch_banded.hip banded_pair)."""
+    dlo = max(min(0, n2 - n1) - w, -n1 - 1024)
+    dhi = min(max(0, n2 - n1) + w, n2 + 1024)
+    iters, nblocks = n2 // 64 + 2, n2 // 64 + 1
+    slots = min(iters, (dhi - dlo + 319 + 63) // 64 + 2)
+    masked = plain = 0
+    for p in range((n1 + 255) // 256):
+        c0 = 256 * p
+        it0 = max(0, (c0 + dlo) >> 6)
+        itl = min(nblocks, ((c0 + 319 + dhi) >> 6) + 1, it0 + slots - 1)
+        for it in range(it0, itl + 1):
+            if 64 * it - c0 - 319 >= dlo and 64 * it + 62 - c0 <= dhi:
+                plain += 1
+            else:
+                masked += 1
+    return masked, plain, ((n1 + 255) // 256) * iters
+
+
+def predict_band(pairs, w):
+    """The banded score kernel's time over the matrix score kernel's on the same pairs, from
+    iteration counts alone: every iteration costs its VALU instructions."""
+    m = pl = al = 0
+    for a, b in pairs:
+        x, y, z = band_iterations(a.size, b.size, w)
+        m, pl, al = m + x, pl + y, al + z
+    return round((m * MASKED_OVER_PLAIN + pl) / al, 3)
+
+
+def run_banded(name):
+    go, ge = args.gap_open, -1
+    letters, mat = make_matrix(20)
+    pairs = make_pairs(name, letters)
+    cells = sum(a.size * b.size for a, b in pairs)
+    e = {"shape": name, "pairs": len(pairs), "cells": int(cells), "gap_open": go, "gap": ge, "letters": 20,
+         "lengths": "uniform %d..%d" % SHAPES[name][1:] if name == "mixed" else "%d x %d" % SHAPES[name][1:]}
+    gs, ga, glob = time_entries(pairs, cells, lambda p, **kw: nwhip.score_batch_matrix(p, mat, ge, go, **kw),
+                                lambda p: nwhip.align_batch_matrix(p, mat, ge, go))
+    e["score_batch_matrix"], e["align_batch_matrix"] = gs, ga
+    for w in args.band:
+        s, a, sc = time_entries(pairs, cells, lambda p, **kw: nwhip.score_batch_banded(p, mat, ge, go, w, **kw),
+                                lambda p: nwhip.align_batch_banded(p, mat, ge, go, w))
+        pred, got = predict_band(pairs, w), round(s["fill_ms"] / gs["fill_ms"], 3)
+        e["band_%d" % w] = {
+            "scores_equal_global": int((sc == glob).sum()), "score_batch_banded": s, "align_batch_banded": a,
+            "score_banded_over_matrix": got, "predicted_score_banded_over_matrix": pred,
+            "explained": bool(abs(got - pred) <= 0.15),
+            "align_fill_banded_over_matrix": round(a["fill_ms"] / ga["fill_ms"], 3),
+            "align_fill_walk_banded_over_matrix": round(a["fill_walk_ms"] / ga["fill_walk_ms"], 3),
+            "dir_bytes_banded_over_matrix": round(a["dir_bytes"] / ga["dir_bytes"], 4)}
+    print(json.dumps(e), flush=True)
+    return e
+
+
 def run(name):
     pairs = make_pairs(name)
     cells = sum(a.size * b.size for a, b in pairs)
@@ -303,7 +374,7 @@ if os.path.exists(args.out):
 rec.update({"device": torch.cuda.get_device_name(0), "library": nwhip.version(), "scheme": list(scheme),
             "reps": args.reps, "sweep_yardstick_gcups": round(SWEEP_GCUPS, 1)})
 for name in (list(SHAPES) if args.shape == "all" else [args.shape]):
-    rec["shapes"][name] = (run_semi(name) if args.ends is not None else run_local(name) if args.local else run_matrix(name) if args.matrix is not None else
+    rec["shapes"][name] = (run_banded(name) if args.band is not None else run_semi(name) if args.ends is not None else run_local(name) if args.local else run_matrix(name) if args.matrix is not None else
                            run(name) if args.gap_open is None else run_affine(name))
 os.makedirs(os.path.dirname(args.out), exist_ok=True)
 with open(args.out, "w") as f:
