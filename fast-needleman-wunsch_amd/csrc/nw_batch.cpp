@@ -19,7 +19,11 @@
 // from the definition.  The banded entries (nw_score_batch_banded_async, nw_score_batch_
 // banded, nw_align_batch_banded; kernels in nw_batch_banded.hip) are the matrix ones with a
 // band width: the Cost carries it, a pair's direction bytes are nw_batch_banded_dir_bytes,
-// and the sweep and the walk are that file's.
+// and the sweep and the walk are that file's.  The two-piece entries (nw_score_batch_dual_
+// async, nw_score_batch_dual, nw_align_batch_dual; kernels in nw_batch_dual.hip) are the
+// matrix ones with a second (open, extend) piece: the Cost carries it, a worker's column
+// scratch is three columns, a pair's direction bytes are nw_batch_dual_dir_bytes, and the
+// sweep and the walk are that file's.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -46,16 +50,23 @@ struct Cost {
     int32_t ends = 0;     // semi: NW_ENDS_* bits
     bool banded = false;  // cells within `band` diagonals only (matrix is then true)
     int32_t band = 0;
+    bool dual = false;  // gap cost max(open + L * gap, open2 + L * gap2) (matrix is then true)
+    int32_t open2 = 0, gap2 = 0;
     bool hits() const { return local || semi; }
     size_t out_bytes() const { return hits() ? sizeof(nw_local_hit) : sizeof(int32_t); }
-    int64_t col_words(int64_t max_n2) const { return nw::batch_col_words(max_n2) * (affine ? 2 : 1); }
+    int64_t col_words(int64_t max_n2) const { return nw::batch_col_words(max_n2) * (dual ? 3 : affine ? 2 : 1); }
     int64_t dir_bytes(int64_t n1, int64_t n2) const {
         if (banded) return nw_batch_banded_dir_bytes(n1, n2, band);
+        if (dual) return nw_batch_dual_dir_bytes(n1, n2);
         return affine ? nw_batch_affine_dir_bytes(n1, n2) : nw_batch_dir_bytes(n1, n2);
     }
     // a pair without cells: one run along the boundary
-    int32_t empty_score(const nw_params *p, int64_t n) const { return (int32_t)((n > 0 ? open : 0) + p->gap * n); }
+    int32_t empty_score(const nw_params *p, int64_t n) const {
+        const int64_t g1 = (n > 0 ? open : 0) + p->gap * n;
+        return (int32_t)(dual && n > 0 ? std::max<int64_t>(g1, open2 + gap2 * n) : g1);
+    }
     bool range_ok(const nw_params *p, int64_t n1, int64_t i_max) const {
+        if (dual) return dual_range_ok(p, open, open2, gap2, mat_abs, n1, i_max);
         if (matrix) return matrix_range_ok(p, open, mat_abs, n1, i_max);
         return affine ? affine_range_ok(p, open, n1, i_max) : w_range_ok(p, n1, i_max);
     }
@@ -101,6 +112,14 @@ Cost banded_cost(const nw_submat *m, int32_t gap_open, int32_t band) {
     Cost c = matrix_cost(m, gap_open);
     c.banded = true;
     c.band = band;
+    return c;
+}
+
+Cost dual_cost(const nw_submat *m, int32_t gap_open, int32_t gap_open2, int32_t gap2) {
+    Cost c = matrix_cost(m, gap_open);
+    c.dual = true;
+    c.open2 = gap_open2;
+    c.gap2 = gap2;
     return c;
 }
 
@@ -179,6 +198,8 @@ int params_check(const nw_params *p, int64_t npairs, const Cost &cost) {
     if (cost.matrix && !valid_submat(cost.mat)) return NW_ERR_ARG;
     if (cost.semi && (cost.ends < 0 || cost.ends > NW_ENDS_OVERLAP)) return NW_ERR_ARG;
     if (cost.banded && cost.band < 0) return NW_ERR_ARG;
+    // piece 2 as piece 1: no positive opening, the extension within nw_params.gap's range
+    if (cost.dual && (cost.open2 > 0 || !valid_gap(cost.gap2))) return NW_ERR_ARG;
     return NW_OK;
 }
 
@@ -296,6 +317,13 @@ int batch_run(nw_ctx *c, const nw::BatchMatrixArgs &ma, const Cost &cost, bool d
         ba.m = ma;
         ba.band = cost.band;
         e = nw::launch_batch_banded(ba, dirs, g, stream);
+    } else if (cost.dual) {
+        nw::BatchDualArgs da;
+        da.m = ma;
+        da.gap_open2 = cost.open2;
+        da.gap2 = cost.gap2;
+        da.eoff2 = 2 * ma.a.eoff;
+        e = nw::launch_batch_dual(da, dirs, g, stream);
     } else
         e = cost.matrix ? nw::launch_batch_matrix(ma, dirs, g, stream)
             : cost.affine ? nw::launch_batch_affine(aa, dirs, g, stream)
@@ -589,7 +617,9 @@ int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
             bw.w = w;
             bw.band = cost.band;
             e = nw::launch_batch_banded_walk(bw, nullptr);
-        } else
+        } else if (cost.dual)  // five states over a byte per cell
+            e = nw::launch_batch_dual_walk(w, nullptr);
+        else
             e = cost.affine ? nw::launch_batch_affine_walk(w, nullptr) : nw::launch_batch_walk(w, nullptr);
         if (e != hipSuccess) return NW_ERR_HIP;
         NW_HIP_TRY(hipEventRecord(ew.b, nullptr));
@@ -643,6 +673,11 @@ int64_t nw_batch_banded_dir_bytes(int64_t n1, int64_t n2, int32_t band) {
     if (n1 < 0 || n2 < 0 || band < 0) return -1;
     if (n1 == 0 || n2 == 0) return 0;
     return nw::batch_strips(n1) * nw::batch_banded_slots(n1, n2, band) * 2 * nw::kBatchDirIter;
+}
+
+int64_t nw_batch_dual_dir_bytes(int64_t n1, int64_t n2) {
+    const int64_t b = nw_batch_affine_dir_bytes(n1, n2);
+    return b < 0 ? b : 2 * b;
 }
 
 int nw_score_batch_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
@@ -771,6 +806,28 @@ int nw_align_batch_banded(const int8_t *s1cat, const int64_t *off1, const int8_t
                           int64_t *n_ops, nw_batch_stats *stats) {
     return align_batch(s1cat, off1, s2cat, off2, npairs, p, banded_cost(m, gap_open, band), o, scores, ops, ops_off,
                        n_ops, stats);
+}
+
+int nw_score_batch_dual_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                              const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2, int64_t max_n2,
+                              const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t gap_open2,
+                              int32_t gap2, int32_t *d_scores, void *stream) {
+    return score_batch_async(c, d_s1cat, d_off1, d_s2cat, d_off2, npairs, total1, total2, max_n2, p,
+                             dual_cost(m, gap_open, gap_open2, gap2), d_scores, stream);
+}
+
+int nw_score_batch_dual(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                        int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t gap_open2,
+                        int32_t gap2, int32_t *scores, nw_batch_stats *stats) {
+    return score_batch(s1cat, off1, s2cat, off2, npairs, p, dual_cost(m, gap_open, gap_open2, gap2), scores, stats);
+}
+
+int nw_align_batch_dual(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                        int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t gap_open2,
+                        int32_t gap2, const nw_batch_opts *o, int32_t *scores, uint8_t *ops, const int64_t *ops_off,
+                        int64_t *n_ops, nw_batch_stats *stats) {
+    return align_batch(s1cat, off1, s2cat, off2, npairs, p, dual_cost(m, gap_open, gap_open2, gap2), o, scores, ops,
+                       ops_off, n_ops, stats);
 }
 
 }  // extern "C"

@@ -158,6 +158,19 @@ constexpr int64_t batch_banded_first(int64_t p, int64_t dlo) {
     return s > 0 ? s >> 6 : 0;
 }
 
+// The two-piece kernels (nw_batch_dual.hip): the matrix launch's arguments as the matrix
+// kernels take them (piece 1 = m.a.gap_open, m.a.b.gap; the w form is taken relative to it:
+// m.wide and m.score as there) and piece 2.  m.a.b.cstride is three times batch_col_words (a
+// worker keeps H', E1' and E2' of a right column: E1' m.a.eoff and E2' eoff2 words behind
+// H'), and the directions kernel writes a byte per cell (four times kBatchDirIter per
+// iteration of a strip).
+struct BatchDualArgs {
+    BatchMatrixArgs m;
+    int32_t gap_open2;  // <= 0
+    int32_t gap2;
+    int64_t eoff2;
+};
+
 // mapped (perm and at most kMaxPerm distinct column characters) or raw copy of s2cat
 int launch_batch_rows(const uint8_t *d_s2, int64_t total2, int32_t perm, const uint8_t *meta, uint8_t *d_rows,
                       void *stream);
@@ -186,5 +199,9 @@ int launch_batch_semi_walk(const BatchSemiWalkArgs &w, void *stream);
 // only, the walk indexes the direction blocks that range leaves
 int launch_batch_banded(const BatchBandedArgs &a, bool dirs, int grid, void *stream);
 int launch_batch_banded_walk(const BatchBandedWalkArgs &w, void *stream);
+// global alignment with the matrix under a two-piece gap cost: the sweep carries five values
+// per cell, the walk is a machine of five states over a byte per cell
+int launch_batch_dual(const BatchDualArgs &a, bool dirs, int grid, void *stream);
+int launch_batch_dual_walk(const BatchWalkArgs &w, void *stream);
 
 }  // namespace nw

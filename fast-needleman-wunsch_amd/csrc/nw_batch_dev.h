@@ -1,6 +1,8 @@
 // nw_batch_dev.h -- device code shared by the batch kernels' files (nw_batch.hip,
-// nw_batch_affine.hip, nw_batch_matrix.hip, nw_batch_local.hip, nw_batch_semi.hip and
-// nw_batch_banded.hip, which runs sweep_tickets and sweep_iter under its own pair loop).
+// nw_batch_affine.hip, nw_batch_matrix.hip, nw_batch_local.hip, nw_batch_semi.hip,
+// nw_batch_banded.hip, which runs sweep_tickets and sweep_iter under its own pair loop, and
+// nw_batch_dual.hip, which runs sweep_tickets and ProfileSub under its own pair and iteration
+// loops and finds its cells' direction bytes by dual_dir_byte).
 // Private to them: every file compiles its own copy (no relocatable device code), so
 // everything here is in the unnamed namespace.
 //
@@ -421,6 +423,18 @@ struct MatrixCell : GlobalCell, ProfileSub {
     const int64_t idx =                                                                                                \
         ((((p * (iters) + (s >> 6)) * 16 + ((s & 63) >> 2)) * 2 + ((s & 3) >> 1)) * 64 + l) * 4 + (s & 1) * 2 + (k >> 1); \
     const uint32_t bits = ((uint32_t)(d)[idx] >> (4 * (k & 1))) & 15u
+
+// ---- the two-piece kernels (nw_batch_dual.hip): the direction byte of a cell ----
+
+// The index of the byte of cell (r, c), r, c >= 1, in the direction block of a pair whose
+// strips have `iters` iterations: one byte per cell, computed in strip p = (c-1) / 256 by
+// lane l = ((c-1) % 256) / 4, column k = (c-1) % 4, at step s = r + l: byte k of dword [p][s]
+// [l] (a strip has 64 * iters steps).  The sweep stores by it, nw_batch_dual_walk reads by it.
+constexpr int64_t dual_dir_byte(int64_t iters, int64_t r, int64_t c) {
+    const int64_t cj = c - 1;
+    const int64_t p = cj >> 8, l = (cj & 255) >> 2, k = cj & 3;
+    return ((p * iters * 64 + r + l) * 64 + l) * 4 + k;
+}
 
 }  // namespace
 }  // namespace nw

@@ -1,5 +1,6 @@
 // nw_bdna.cpp -- host helpers of libnwhip.so: .bdna I/O and the seeded
 // synthetic-sequence generator (declared in include/nw_hip.h).
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 
@@ -133,6 +134,32 @@ int nw_ops_score_matrix(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t 
             sum += m->score[m->index[(uint8_t)s1[j]] * NW_SUBMAT_MAX + m->index[(uint8_t)s2[i]]];
         prev = op;
     });
+    if (st == NW_OK) *score = sum;
+    return st;
+}
+
+int nw_ops_score_dual(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t begin_i, int64_t begin_j,
+                      const uint8_t *ops, int64_t n_ops, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                      int32_t gap_open2, int32_t gap2, int64_t *score) {
+    if (!p || !score || !m || m->n < 1 || m->n > NW_SUBMAT_MAX) return NW_ERR_ARG;
+    if (m->reserved[0] != 0 || m->reserved[1] != 0 || m->reserved[2] != 0) return NW_ERR_ARG;
+    for (int b = 0; b < 256; ++b)
+        if (m->index[b] >= m->n) return NW_ERR_ARG;
+    int64_t sum = 0, run = 0;  // run: ops of the maximal run of ups or of lefts that is open
+    uint8_t prev = 0;          // (a diag: the first gap op opens a run)
+    auto close = [&]() {       // the run, priced whole by its better piece
+        if (run > 0) sum += std::max((int64_t)gap_open + run * p->gap, (int64_t)gap_open2 + run * gap2);
+        run = 0;
+    };
+    const int st = walk_ops(s1, n1, s2, n2, begin_i, begin_j, ops, n_ops, [&](int64_t, uint8_t op, int64_t i, int64_t j) {
+        if (op != prev) close();
+        if (op != 0)
+            run += 1;
+        else
+            sum += m->score[m->index[(uint8_t)s1[j]] * NW_SUBMAT_MAX + m->index[(uint8_t)s2[i]]];
+        prev = op;
+    });
+    close();
     if (st == NW_OK) *score = sum;
     return st;
 }

@@ -105,12 +105,15 @@ Shape make_shape(int64_t n1, int64_t n2, int32_t waves_req, int32_t sub_req, int
 int32_t band_kernel(int32_t k);
 bool shape_valid(const Shape &s);
 bool valid_params(const nw_params *p);
+bool valid_gap(int32_t gap);  // what valid_params admits as nw_params.gap in NW_MODE_NW
 int tb_args(int64_t n1, int64_t n2, const nw_params *p, const nw_tb_opts *o, const uint8_t *ops, int64_t ops_cap,
             const nw_alignment *out, int32_t *band, int32_t *maxwin, int32_t *aim);
 // ---- nw_launch.cpp: what every strip-chain launch shares
 bool w_range_ok(const nw_params *p, int64_t n1, int64_t i_max);
 bool affine_range_ok(const nw_params *p, int32_t gap_open, int64_t n1, int64_t i_max);
 bool matrix_range_ok(const nw_params *p, int32_t gap_open, int64_t max_abs, int64_t n1, int64_t i_max);
+bool dual_range_ok(const nw_params *p, int32_t gap_open, int32_t gap_open2, int32_t gap2, int64_t max_abs, int64_t n1,
+                   int64_t i_max);
 bool perm_allowed(const nw_params *p, int32_t off);
 int launch_workspace(nw_ctx *c, const Shape &s, uint64_t ntags, int32_t nbl, void *stream, int64_t *qlen);
 // ---- nw_hostpath.cpp: the one-shot entries' device and its kept context, held

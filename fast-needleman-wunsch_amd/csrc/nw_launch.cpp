@@ -51,6 +51,25 @@ bool matrix_range_ok(const nw_params *p, int32_t gap_open, int64_t max_abs, int6
     return 3 * std::llabs((long long)gap_open) + (m + std::llabs(p->gap)) * (long long)(n1 + i_max + 2) < (1LL << 28);
 }
 
+// The two-piece kernels hold H, E1, F1, E2 and F2 minus ge1 * (i + j).  With G = max(|go1|,
+// |go2|), A = max(|ge1|, |ge2|) and M = max(A, max_abs): every path to (i, j) has at most i +
+// j steps, each worth at most M in absolute value, plus openings; H is at least the score of
+// the path "one run up, one run left" (two openings) and at most M * (i + j) (openings are
+// <= 0), an Et or Ft is at most H and at least a neighbour's H plus one opening and one
+// extension: |X| <= 3 G + M * (i + j + 1) for all five.  The form subtracts ge1 * (i + j),
+// which costs at most A * (i + j) more -- this covers the drift of the piece-2 values, which
+// is (ge2 - ge1) per step only relative to values that drift by -ge1 themselves -- and the
+// cell's sums (H' + go_t, H'_diag + s - 2 ge1, max(..) + ge2 - ge1) add at most one opening
+// or 2 A + M once, the "+ 2".  So the matrix bound with G and A in the place of |gap_open|
+// and |gap| keeps every real value above -2^28, and the -2^29 is added to at most once.
+bool dual_range_ok(const nw_params *p, int32_t gap_open, int32_t gap_open2, int32_t gap2, int64_t max_abs, int64_t n1,
+                   int64_t i_max) {
+    const long long g = std::max(std::llabs((long long)gap_open), std::llabs((long long)gap_open2));
+    const long long a = std::max(std::llabs((long long)p->gap), std::llabs((long long)gap2));
+    const long long m = std::max<long long>(max_abs, a);
+    return 3 * g + (m + a) * (long long)(n1 + i_max + 2) < (1LL << 28);
+}
+
 // v_perm score tables when every substitution score minus `off` fits int8 (the
 // kernel falls back to compares on the device when s1 holds more than kMaxPerm
 // distinct characters).  off: the table bytes are s - 2 GAP in the w form (NW, and

@@ -121,6 +121,9 @@ bool shape_valid(const Shape &s) {
     return s.kernel == NW_KERNEL_PANELS ? nw::panel_shape_ok(s.K, s.NC) : nw::shape_ok(s.K, s.NC);
 }
 
+// the range of nw_params.gap (and of the two-piece entries' gap2)
+bool valid_gap(int32_t gap) { return std::abs(gap) < (1 << 12); }
+
 bool valid_params(const nw_params *p) {
     if (!p) return false;
     if (p->mode != NW_MODE_NW && p->mode != NW_MODE_SW) return false;
@@ -140,7 +143,7 @@ bool valid_params(const nw_params *p) {
     if ((p->flags & dbg) != 0 && (p->flags & NW_FLAG_TIMING_ONLY) == 0) return false;
     // keep every intermediate far from int32 overflow (|score| < 2^29)
     const int32_t lim = 1 << 12;
-    return std::abs(p->match) < lim && std::abs(p->mismatch) < lim && std::abs(p->gap) < lim;
+    return std::abs(p->match) < lim && std::abs(p->mismatch) < lim && valid_gap(p->gap);
 }
 
 // Arguments of nw_traceback / nw_align that need no device to judge; on NW_OK the

@@ -7,7 +7,7 @@
 //   --mem BYTES / --block-rows K: align in linear memory (nw_align_ckpt) within BYTES
 //   of device memory / in blocks of K rows (a multiple of 64); the output is the same.
 //   --score-only: no alignment, the score from the table-free sweep (nw_score).
-//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only] [--gap-open G] [--matrix FILE] [--local | --ends N | --band W]
+//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only] [--gap-open G] [--matrix FILE] [--local | --ends N | --band W | --gap2 O2,E2]
 //   LIST: a text file, one pair "A.bdna B.bdna" per line (paths relative to the
 //   list's directory unless absolute); all pairs are aligned in ONE call
 //   (nw_align_batch; --score-only: nw_score_batch).  stdout: "<ms>\n", then one
@@ -40,6 +40,12 @@
 //   alignment (nw_align_batch_banded / nw_score_batch_banded): only paths that stay within
 //   W diagonals of the pair's own (of 0 .. |B| - |A|) count.  Substitution as --local's
 //   (--matrix, or --scheme's match / mismatch over A, C, G, T); one "Score:" line per pair.
+//   --gap2 O2,E2 (with --batch only, not with --local, --ends or --band; O2 <= 0): a second
+//   piece of the gap cost (nw_align_batch_dual / nw_score_batch_dual): a gap of length L
+//   costs max(G + L * g, O2 + L * E2), G from --gap-open (default 0) and g from --scheme --
+//   short gaps by the steep piece, long ones by the flat piece (minimap2's -O4,24 -E2,1 is
+//   --scheme 2,-4,-2 --gap-open -4 --gap2 -24,-1).  Substitution as --band's; one "Score:"
+//   line per pair.
 // Argument and missing-file errors are nw_driver's (exit 1); a device failure is
 // reported on stderr and exits 2.
 #include <chrono>
@@ -165,15 +171,16 @@ static std::string row_text(const std::vector<int8_t> &row) {
 
 // --batch LIST: every pair of the list in one call
 static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bool score_only, const int32_t *gap_open,
-                     const char *matrix, bool local, int ends, int64_t band) {
+                     const char *matrix, bool local, int ends, int64_t band, const int32_t *gap2) {
     nw_submat mat;
     bool listed[256];
     const bool semi = ends >= 0;
     const bool banded = band >= 0;
     const bool hit_lines = local || semi;  // a result is an nw_local_hit
-    if ((hit_lines || banded) && matrix == nullptr) {
+    const bool dual = gap2 != nullptr;  // gap2[0] the opening, gap2[1] the extension of piece 2
+    if ((hit_lines || banded || dual) && matrix == nullptr) {
         if (p.match < -128 || p.match > 127 || p.mismatch < -128 || p.mismatch > 127) {
-            std::cout << "error: " << (local ? "--local" : semi ? "--ends" : "--band")
+            std::cout << "error: " << (local ? "--local" : semi ? "--ends" : banded ? "--band" : "--gap2")
                       << " without --matrix needs match and mismatch in -128..127" << std::endl;
             return 1;
         }
@@ -214,7 +221,7 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
                 std::cout << "ERROR: no such file " << path << std::endl;
                 return 1;
             }
-            if (matrix != nullptr || hit_lines || banded)
+            if (matrix != nullptr || hit_lines || banded || dual)
                 for (int64_t x = 0; x < n; ++x)
                     if (!listed[(unsigned char)s[x]]) {
                         std::cout << "ERROR: byte " << (int)(unsigned char)s[x] << " of " << path
@@ -256,6 +263,12 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
                         : nw_align_batch_banded(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
                                                 gap_open ? *gap_open : 0, (int32_t)band, &bo, scores.data(),
                                                 ops.data(), ops_off.data(), n_ops.data(), nullptr);
+    else if (dual)
+        st = score_only ? nw_score_batch_dual(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
+                                              gap_open ? *gap_open : 0, gap2[0], gap2[1], scores.data(), nullptr)
+                        : nw_align_batch_dual(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
+                                              gap_open ? *gap_open : 0, gap2[0], gap2[1], &bo, scores.data(),
+                                              ops.data(), ops_off.data(), n_ops.data(), nullptr);
     else if (matrix != nullptr)
         st = score_only ? nw_score_batch_matrix(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
                                                 gap_open ? *gap_open : 0, scores.data(), nullptr)
@@ -314,6 +327,8 @@ int main(int argc, char **argv) {
     bool affine = false, local = false;
     int ends = -1;  // --ends N: semi-global
     long long band = -1;  // --band W: banded global
+    int32_t gap2[2] = {0, 0};  // --gap2 O2,E2: the second piece of the gap cost
+    bool dual = false;
     for (int a = 1; a < argc; ++a) {
         if (std::strcmp(argv[a], "--scheme") == 0) {
             int m, mm, g;
@@ -369,6 +384,17 @@ int main(int argc, char **argv) {
             }
             band = v;
             ++a;
+        } else if (std::strcmp(argv[a], "--gap2") == 0) {
+            int o2 = 0, e2 = 0;
+            char tail = 0;
+            if (a + 1 >= argc || std::sscanf(argv[a + 1], "%d,%d%c", &o2, &e2, &tail) != 2 || o2 > 0) {
+                std::cout << "error: --gap2 expects open,extend with open <= 0" << std::endl;
+                return 1;
+            }
+            gap2[0] = o2;
+            gap2[1] = e2;
+            dual = true;
+            ++a;
         } else if (std::strcmp(argv[a], "--score-only") == 0) {
             score_only = true;
         } else if (std::strcmp(argv[a], "--batch") == 0) {
@@ -384,7 +410,7 @@ int main(int argc, char **argv) {
     if (batch != nullptr) {
         if (!pos.empty() || co.block_rows != 0) {
             std::cout << "error: --batch takes the list alone (and --scheme, --mem, --score-only, --gap-open, "
-                         "--matrix, --local, --ends, --band)"
+                         "--matrix, --local, --ends, --band, --gap2)"
                       << std::endl;
             return 1;
         }
@@ -397,6 +423,11 @@ int main(int argc, char **argv) {
                       << " (the band is built for the global alignment only)" << std::endl;
             return 1;
         }
+        if (dual && (local || ends >= 0 || band >= 0)) {
+            std::cout << "error: --gap2 cannot be combined with " << (local ? "--local" : ends >= 0 ? "--ends" : "--band")
+                      << " (the two-piece gap cost is built for the global alignment only)" << std::endl;
+            return 1;
+        }
         if (local) {
             if (p.gap > 0) {
                 std::cout << "error: --local needs a gap of at most 0 (--scheme's third number)" << std::endl;
@@ -404,7 +435,13 @@ int main(int argc, char **argv) {
             }
             p.mode = NW_MODE_SW;
         }
-        return run_batch(batch, p, co.mem_bytes, score_only, affine ? &gap_open : nullptr, matrix, local, ends, band);
+        return run_batch(batch, p, co.mem_bytes, score_only, affine ? &gap_open : nullptr, matrix, local, ends, band,
+                         dual ? gap2 : nullptr);
+    }
+    if (dual) {
+        std::cout << "error: --gap2 needs --batch (the two-piece gap cost is built for the batched alignment only)"
+                  << std::endl;
+        return 1;
     }
     if (band >= 0) {
         std::cout << "error: --band needs --batch (the band is built for the batched alignment only)" << std::endl;

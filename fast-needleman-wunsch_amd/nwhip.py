@@ -50,7 +50,9 @@ EXPORTS = ["nw_params_default", "nw_strerror", "nw_version", "nw_fill", "nw_tabl
            "nw_score_batch_local_async", "nw_score_batch_local", "nw_align_batch_local",
            "nw_score_batch_semi_async", "nw_score_batch_semi", "nw_align_batch_semi",
            "nw_batch_banded_dir_bytes", "nw_score_batch_banded_async", "nw_score_batch_banded",
-           "nw_align_batch_banded"]
+           "nw_align_batch_banded",
+           "nw_batch_dual_dir_bytes", "nw_score_batch_dual_async", "nw_score_batch_dual", "nw_align_batch_dual",
+           "nw_ops_score_dual"]
 IPC_HANDLE_BYTES = 64
 
 
@@ -299,6 +301,21 @@ def lib() -> ctypes.CDLL:
     L.nw_align_batch_banded.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams), _smp,
                                         ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(NwBatchOpts), _i32p, _u8p,
                                         _i64p_, _i64p_, ctypes.POINTER(NwBatchStats)]
+    L.nw_batch_dual_dir_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
+    L.nw_batch_dual_dir_bytes.restype = ctypes.c_int64
+    L.nw_score_batch_dual_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.POINTER(NwParams), _smp, ctypes.c_int32,
+                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    L.nw_score_batch_dual.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams), _smp,
+                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p,
+                                      ctypes.POINTER(NwBatchStats)]
+    L.nw_align_batch_dual.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams), _smp,
+                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(NwBatchOpts),
+                                      _i32p, _u8p, _i64p_, _i64p_, ctypes.POINTER(NwBatchStats)]
+    L.nw_ops_score_dual.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                    _u8p, ctypes.c_int64, ctypes.POINTER(NwParams), _smp, ctypes.c_int32,
+                                    ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
     L.nw_debug_tb_shift.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                     ctypes.c_int64]
     L.nw_debug_tb_shift.restype = ctypes.c_int64
@@ -977,6 +994,78 @@ def align_batch_banded(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, 
     return scores[:n], out, stats
 
 
+def batch_dual_dir_bytes(n1: int, n2: int) -> int:
+    """Direction bytes of one pair in align_batch_dual (nw_batch_dual_dir_bytes): a byte per
+    cell, 2 * batch_affine_dir_bytes(n1, n2); 0 for an empty side, -1 for a negative size."""
+    return int(lib().nw_batch_dual_dir_bytes(int(n1), int(n2)))
+
+
+def score_batch_dual(pairs, mat: SubMatrix, gap: int = -2, gap_open: int = -4, gap2: int = -1, gap_open2: int = -24,
+                     waves: int = 0, device: int = -1, return_stats: bool = False):
+    """score_batch_matrix under a two-piece gap cost (nw_score_batch_dual): a run of L ups
+    or of L lefts costs max(gap_open + L * gap, gap_open2 + L * gap2) -- short indels by the
+    steep piece, long ones by the flat piece.  Equal pieces give score_batch_matrix's scores."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    mat.check(s1, s2)
+    n = len(pairs)
+    scores = np.zeros(max(n, 1), np.int32)
+    stats = NwBatchStats()
+    p = params((1, 0, int(gap)), waves, device)
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_score_batch_dual(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
+                                   off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
+                                   int(gap_open), int(gap_open2), int(gap2), scores.ctypes.data_as(_i32p),
+                                   ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_score_batch_dual")
+    return (scores[:n], stats) if return_stats else scores[:n]
+
+
+def align_batch_dual(pairs, mat: SubMatrix, gap: int = -2, gap_open: int = -4, gap2: int = -1, gap_open2: int = -24,
+                     mem_bytes: int = 0, waves: int = 0, device: int = -1):
+    """align_batch_matrix under a two-piece gap cost (nw_align_batch_dual): (scores, [ops of
+    pair 0, ..], NwBatchStats).  The ops are 0 / 1 / 2 as everywhere: they do not say which
+    piece priced a run (ops_score_dual takes the better one per run)."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    mat.check(s1, s2)
+    n = len(pairs)
+    ops_off = off1 + off2
+    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
+    scores = np.zeros(max(n, 1), np.int32)
+    n_ops = np.zeros(max(n, 1), np.int64)
+    stats = NwBatchStats()
+    p = params((1, 0, int(gap)), waves, device)
+    o = NwBatchOpts(int(mem_bytes))
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_align_batch_dual(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
+                                   off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
+                                   int(gap_open), int(gap_open2), int(gap2), ctypes.byref(o),
+                                   scores.ctypes.data_as(_i32p), ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                   ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_align_batch_dual")
+    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
+    return scores[:n], out, stats
+
+
+def ops_score_dual(s1, s2, ops, mat: SubMatrix, gap: int = -2, gap_open: int = -4, gap2: int = -1,
+                   gap_open2: int = -24, begin=(0, 0)) -> int:
+    """Score of an alignment's ops under a matrix and the two-piece gap cost (nw_ops_score_dual):
+    every maximal run of L ups or of L lefts adds max(gap_open + L * gap, gap_open2 + L * gap2)."""
+    a, b = _seq(s1), _seq(s2)
+    mat.check(a, b)
+    o = np.ascontiguousarray(np.asarray(ops, dtype=np.uint8))
+    p = params((1, 0, int(gap)))
+    sc = ctypes.c_int64()
+    st = lib().nw_ops_score_dual(a.ctypes.data_as(_i8p), a.size, b.ctypes.data_as(_i8p), b.size, int(begin[0]),
+                                 int(begin[1]), o.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), o.size,
+                                 ctypes.byref(p), ctypes.byref(mat.c), int(gap_open), int(gap_open2), int(gap2),
+                                 ctypes.byref(sc))
+    if st != NW_OK:
+        raise NwError(st, "nw_ops_score_dual")
+    return int(sc.value)
+
+
 def ops_score_matrix(s1, s2, ops, mat: SubMatrix, gap: int = -1, gap_open: int = 0, begin=(0, 0)) -> int:
     """Score of an alignment's ops under a matrix and affine gap cost (nw_ops_score_matrix)."""
     a, b = _seq(s1), _seq(s2)
@@ -1532,7 +1621,7 @@ class Context:
         return int(sc.item()), (gran & 0xFFFFFFFF).to(torch.int32)
 
     def score_batch(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, scheme=(1, 0, -1), stream=None,
-                    waves: int = 0, flags: int = 0, gap_open=None, mat=None, band=None):
+                    waves: int = 0, flags: int = 0, gap_open=None, mat=None, band=None, piece2=None):
         """Scores of a batch on device tensors (nw_score_batch_async): d_s1cat / d_s2cat
         int8/uint8 CUDA tensors (the concatenations), d_off1 / d_off2 int64 CUDA tensors of
         npairs + 1 offsets, max_n2 >= every pair's n2.  Returns an int32 CUDA tensor of
@@ -1540,7 +1629,8 @@ class Context:
         synchronised.  Pairs are claimed in index order: submit them longest first.
         gap_open (an int): affine gap cost, see score_batch_affine (Context.score_batch_affine).
         mat (a SubMatrix): substitution by matrix, see Context.score_batch_matrix.
-        band (an int, with mat): inside a band, see Context.score_batch_banded."""
+        band (an int, with mat): inside a band, see Context.score_batch_banded.
+        piece2 ((gap_open2, gap2), with mat): two-piece gap cost, see Context.score_batch_dual."""
         import torch
         npairs = int(d_off1.numel()) - 1
         assert d_off1.dtype == torch.int64 and d_off2.dtype == torch.int64 and int(d_off2.numel()) == npairs + 1
@@ -1555,7 +1645,11 @@ class Context:
                 ctypes.c_void_p(d_s2cat.data_ptr() if t2 else 0), ctypes.c_void_p(d_off2.data_ptr()), npairs, t1, t2,
                 int(max_n2), ctypes.byref(p))
         tail = (ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(stream.cuda_stream))
-        if mat is not None and band is not None:
+        if mat is not None and piece2 is not None:
+            st, what = lib().nw_score_batch_dual_async(*head, ctypes.byref(mat.c), int(gap_open or 0),
+                                                       int(piece2[0]), int(piece2[1]), *tail), \
+                "nw_score_batch_dual_async"
+        elif mat is not None and band is not None:
             st, what = lib().nw_score_batch_banded_async(*head, ctypes.byref(mat.c), int(gap_open or 0),
                                                          _band32(band), *tail), "nw_score_batch_banded_async"
         elif mat is not None:
@@ -1594,6 +1688,15 @@ class Context:
             raise ValueError("Context.score_batch_banded needs a matrix with other= (it cannot check the sequences)")
         return self.score_batch(d_s1cat, d_off1, d_s2cat, d_off2, max_n2, (1, 0, int(gap)), stream, waves, 0,
                                 gap_open=int(gap_open), mat=mat, band=int(band))
+
+    def score_batch_dual(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, mat: SubMatrix, gap: int = -2,
+                         gap_open: int = -4, gap2: int = -1, gap_open2: int = -24, stream=None, waves: int = 0):
+        """Context.score_batch_matrix under the two-piece gap cost max(gap_open + L * gap,
+        gap_open2 + L * gap2) per run of L (nw_score_batch_dual_async, score_batch_dual)."""
+        if mat.other is None and not mat.listed.all():
+            raise ValueError("Context.score_batch_dual needs a matrix with other= (it cannot check the sequences)")
+        return self.score_batch(d_s1cat, d_off1, d_s2cat, d_off2, max_n2, (1, 0, int(gap)), stream, waves, 0,
+                                gap_open=int(gap_open), mat=mat, piece2=(int(gap_open2), int(gap2)))
 
     def score_batch_local(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, mat: SubMatrix, gap: int = -1,
                           gap_open: int = 0, stream=None, waves: int = 0):

@@ -743,6 +743,72 @@ int nw_align_batch_banded(const int8_t *s1cat, const int64_t *off1, const int8_t
                           const nw_batch_opts *o, int32_t *scores, uint8_t *ops, const int64_t *ops_off,
                           int64_t *n_ops, nw_batch_stats *stats);
 
+/* Batched global alignment under a TWO-PIECE affine gap cost ----------------------
+ * For long reads and genome-to-genome pairs: a run of k consecutive ups, or of k
+ * consecutive lefts, costs
+ *   g(k) = max(go1 + k*ge1, go2 + k*ge2)
+ * -- a short indel is priced by the steep piece, a long deletion or an intron by the flat
+ * one (minimap2's -O4,24 -E2,1 is go = -4, -24 and ge = -2, -1).  The entries are the matrix
+ * entries' with `int32_t gap_open2, int32_t gap2` after gap_open: piece 1 is (gap_open,
+ * nw_params.gap) = (go1, ge1), piece 2 is (gap_open2, gap2) = (go2, ge2), s comes from the
+ * nw_submat exactly as in the matrix entries.
+ *   E_t[i][j] = max(E_t[i][j-1] + ge_t, H[i][j-1] + go_t + ge_t)      t = 1, 2
+ *   F_t[i][j] = max(F_t[i-1][j] + ge_t, H[i-1][j] + go_t + ge_t)
+ *   H[i][j]   = max(H[i-1][j-1] + s, F_1[i][j], E_1[i][j], F_2[i][j], E_2[i][j])
+ *   H[0][0] = 0, H[0][j] = g(j), H[i][0] = g(i), E_t[i][0] = F_t[0][j] = -inf
+ * score = H[n2][n1].  It equals the maximum over all global paths of the sum of s over the
+ * diagonal steps plus g(k) for every maximal run of ups and every maximal run of lefts; an
+ * up-run directly followed by a left-run is two gaps.  With go1, go2 <= 0 splitting one run
+ * into two gaps (which the recurrence can do: a run of one piece may open from an H that a
+ * run of the other piece made) never beats pricing it whole by one piece: g is convex in k
+ * and max(go1, go2), its value at 0, is <= 0, so g(a) + g(b) <= g(a + b).  So the ops alone
+ * determine the score: nw_ops_score_dual computes exactly that sum, with the max per run.
+ * The ops are the walk of a machine of five states from (n2, n1) to (0, 0): in H on row 0
+ * it goes left, on column 0 up; in H at an inner cell it takes the first of diag, F_1, E_1,
+ * F_2, E_2 that equals H (diag: op 0; the others: change state, no op); in F_t it emits op
+ * 1, moves up and returns to H when F_t[i][j] == H[i-1][j] + go_t + ge_t (opening wins a tie
+ * over extending), else stays; E_t likewise with op 2 and a move left.  Ops are 0 / 1 / 2 as
+ * everywhere; they do not say which piece priced a run.
+ * Reductions, byte for byte in scores, ops and n_ops: equal pieces give the matrix
+ * entries' results; so does a piece 2 that is nowhere above piece 1 (go2 <= go1 and ge2 <=
+ * ge1: F_2 <= F_1 and E_2 <= E_1 everywhere, and the order diag, F_1, E_1, F_2, E_2 never
+ * reaches them); a piece 1 strictly below piece 2 (go1 + ge1 < go2 + ge2 and ge1 <= ge2)
+ * gives the matrix entries' results under piece 2.
+ * The CSR layout, options, statistics, slot sizes (n1 + n2), chunking under mem_bytes,
+ * longest-first tickets and the INT32_MIN of a pair longer than max_n2 in the _async form
+ * are the matrix entries'; a pair with an empty side scores g(max(n1, n2)) (0 for 0 x 0),
+ * ops all ups / all lefts.  Refusals and their order are the matrix entries'; then
+ * NW_ERR_ARG for gap_open2 > 0, for gap2 outside nw_params.gap's range (|gap2| < 4096;
+ * positive extensions are legal as there), and for a pair beyond the int32 range of the
+ * kernel's form: it holds H, E_t and F_t minus ge1*(i+j) next to a "minus infinity" of
+ * -2^29 (piece 1 extends for free, piece 2 for one add of ge2 - ge1), and with G =
+ * max(|go1|, |go2|), A = max(|ge1|, |ge2|), M = max(A, max |score[x][y]| over x, y < n)
+ *   3*G + (M + A) * (n1 + n2 + 2) < 2^28
+ * keeps every one of them above -2^28: a value is a path sum of at most i + j steps of at
+ * most M each and at most three openings, and the subtracted ge1*(i+j) is at most A*(i+j)
+ * -- which also covers the piece-2 values' drift of ge2 - ge1 per step (the _async form
+ * checks it for n1 = 0, n2 = max_n2).  Kernels: csrc/nw_batch_dual.hip; a worker keeps
+ * three columns between strips, the directions are one byte per cell.
+ *
+ * nw_batch_dual_dir_bytes: direction bytes of one pair in nw_align_batch_dual, 2 *
+ * nw_batch_affine_dir_bytes(n1, n2).  0 when a side is empty, -1 for a negative size.
+ * Host only. */
+int64_t nw_batch_dual_dir_bytes(int64_t n1, int64_t n2);
+
+int nw_score_batch_dual_async(nw_ctx *ctx, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                              const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2, int64_t max_n2,
+                              const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t gap_open2,
+                              int32_t gap2, int32_t *d_scores, void *stream);
+
+int nw_score_batch_dual(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                        int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t gap_open2,
+                        int32_t gap2, int32_t *scores, nw_batch_stats *stats);
+
+int nw_align_batch_dual(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                        int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open, int32_t gap_open2,
+                        int32_t gap2, const nw_batch_opts *o, int32_t *scores, uint8_t *ops, const int64_t *ops_off,
+                        int64_t *n_ops, nw_batch_stats *stats);
+
 /* Launch-only variant for timing loops: no synchronisation, no readback. */
 int nw_fill_device_async(nw_ctx *ctx, const int8_t *d_s1, int64_t n1,
                          const int8_t *d_s2, int64_t n2, const nw_params *p,
@@ -1001,6 +1067,12 @@ int nw_ops_score_affine(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t 
 int nw_ops_score_matrix(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t begin_i,
                         int64_t begin_j, const uint8_t *ops, int64_t n_ops, const nw_params *p, const nw_submat *m,
                         int32_t gap_open, int64_t *score);
+/* nw_ops_score_dual: nw_ops_score_matrix under the two-piece gap cost of the nw_*_batch_dual
+ *   entries: every maximal run of k ops 1, or of k ops 2, adds max(gap_open + k * gap,
+ *   gap_open2 + k * gap2); an up-run directly followed by a left-run is two runs. */
+int nw_ops_score_dual(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2, int64_t begin_i,
+                      int64_t begin_j, const uint8_t *ops, int64_t n_ops, const nw_params *p, const nw_submat *m,
+                      int32_t gap_open, int32_t gap_open2, int32_t gap2, int64_t *score);
 
 #ifdef __cplusplus
 }

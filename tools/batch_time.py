@@ -47,6 +47,16 @@ library's one-pair path, unchanged by the batch; its scores must equal the batch
                     iterations a strip sweeps (predict_band).  Writes
                     profiles/batch_banded_time.json.
 
+  --gap2 O2,E2      the two-piece entries (nw_score_batch_dual, nw_align_batch_dual) on --matrix's pairs
+                    and matrix: a run of L costs max(G + L * g, O2 + L * E2) with G = --gap-open
+                    (default -4) and g = -2 (minimap2's -O4,24 -E2,1 with --gap2 -24,-1).  In the
+                    same process, before them, the matrix entries on the SAME pairs and matrix under
+                    piece 1 alone (the yardstick: code the second piece does not touch) and the
+                    ratios, the score kernels' next to the ratio predicted from the instructions a
+                    64-step iteration issues (predict_dual).  Writes
+                    profiles/batch_dual_time.json.  (A value that starts with a minus sign is
+                    written with the equals sign: --gap2=-24,-1.)
+
 The score kernel's yardstick is the checkpoint sweep's pace on one huge table
 (profiles/ckpt_time.json: 262144^2 in 20.62 ms); `fraction_of_sweep_pace` states it.
 """
@@ -77,14 +87,21 @@ ap.add_argument("--matrix", type=int, default=None, nargs="?", const=20)
 ap.add_argument("--local", action="store_true")
 ap.add_argument("--ends", type=int, default=None, nargs="+")
 ap.add_argument("--band", type=int, default=None, nargs="+")
+ap.add_argument("--gap2", default=None)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
-if args.local or args.ends is not None or args.band is not None:
+if args.gap2 is not None:
+    args.gap2 = tuple(int(x) for x in args.gap2.split(","))
+    assert len(args.gap2) == 2
+    if args.gap_open is None:
+        args.gap_open = -4
+if args.local or args.ends is not None or args.band is not None or args.gap2 is not None:
     args.matrix = 20
 if args.matrix is not None and args.gap_open is None:
     args.gap_open = -11
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "batch_banded_time.json" if args.band is not None else
+    args.out = os.path.join(ROOT, "profiles", "batch_dual_time.json" if args.gap2 is not None else
+                            "batch_banded_time.json" if args.band is not None else
                             "batch_semi_time.json" if args.ends is not None else
                             "batch_local_time.json" if args.local else
                             "batch_matrix_time.json" if args.matrix is not None else
@@ -330,6 +347,54 @@ def run_banded(name):
     return e
 
 
+# Instructions a 64-step iteration of the score kernels issues, from their ISA (the narrow
+# form, which these costs take): VALU + v_readlane + v_writelane of the plain iteration's
+# block and of the EDGE iteration's, two-piece kernel and matrix kernel
+DUAL_ITER = {"plain": 3710 + 384 + 189, "edge": 4769 + 384 + 189}
+MATRIX_ITER = {"plain": 1721 + 256 + 126, "edge": 2466 + 256 + 126}
+
+
+def predict_dual(pairs):
+    """The two-piece score kernel's time over the matrix score kernel's on the same pairs: both
+    run the same iterations, every iteration costs the instructions it issues."""
+    plain = edge = 0
+    for a, b in pairs:
+        nblocks = b.size // 64 + 1
+        e = sum(1 for it in range(nblocks + 1) if it == 0 or 64 * it + 63 > b.size)
+        strips = (a.size + 255) // 256
+        edge, plain = edge + strips * e, plain + strips * (nblocks + 1 - e)
+    cost = lambda c: plain * c["plain"] + edge * c["edge"]
+    return round(cost(DUAL_ITER) / cost(MATRIX_ITER), 3)
+
+
+def run_dual(name):
+    go, ge = args.gap_open, -2
+    go2, ge2 = args.gap2
+    letters, mat = make_matrix(20)
+    pairs = make_pairs(name, letters)
+    cells = sum(a.size * b.size for a, b in pairs)
+    e = {"shape": name, "pairs": len(pairs), "cells": int(cells), "gap_open": go, "gap": ge, "gap_open2": go2,
+         "gap2": ge2, "letters": 20, "matrix_entries": [int(mat.scores.min()), int(mat.scores.max())],
+         "lengths": "uniform %d..%d" % SHAPES[name][1:] if name == "mixed" else "%d x %d" % SHAPES[name][1:]}
+    gs, ga, glob = time_entries(pairs, cells, lambda p, **kw: nwhip.score_batch_matrix(p, mat, ge, go, **kw),
+                                lambda p: nwhip.align_batch_matrix(p, mat, ge, go))
+    dual = dict(gap=ge, gap_open=go, gap2=ge2, gap_open2=go2)
+    s, a, sc = time_entries(pairs, cells, lambda p, **kw: nwhip.score_batch_dual(p, mat, **dual, **kw),
+                            lambda p: nwhip.align_batch_dual(p, mat, **dual))
+    assert (sc >= glob).all()   # (a second piece can only raise a score)
+    pred, got = predict_dual(pairs), round(s["fill_ms"] / gs["fill_ms"], 3)
+    e["score_batch_matrix"], e["align_batch_matrix"] = gs, ga
+    e["score_batch_dual"], e["align_batch_dual"] = s, a
+    e["pairs_the_second_piece_raises"] = int((sc > glob).sum())
+    e["score_dual_over_matrix"], e["predicted_score_dual_over_matrix"] = got, pred
+    e["explained"] = bool(abs(got - pred) <= 0.15)
+    e["align_fill_dual_over_matrix"] = round(a["fill_ms"] / ga["fill_ms"], 3)
+    e["align_fill_walk_dual_over_matrix"] = round(a["fill_walk_ms"] / ga["fill_walk_ms"], 3)
+    e["dir_bytes_dual_over_matrix"] = round(a["dir_bytes"] / ga["dir_bytes"], 4)
+    print(json.dumps(e), flush=True)
+    return e
+
+
 def run(name):
     pairs = make_pairs(name)
     cells = sum(a.size * b.size for a, b in pairs)
@@ -374,7 +439,7 @@ if os.path.exists(args.out):
 rec.update({"device": torch.cuda.get_device_name(0), "library": nwhip.version(), "scheme": list(scheme),
             "reps": args.reps, "sweep_yardstick_gcups": round(SWEEP_GCUPS, 1)})
 for name in (list(SHAPES) if args.shape == "all" else [args.shape]):
-    rec["shapes"][name] = (run_banded(name) if args.band is not None else run_semi(name) if args.ends is not None else run_local(name) if args.local else run_matrix(name) if args.matrix is not None else
+    rec["shapes"][name] = (run_dual(name) if args.gap2 is not None else run_banded(name) if args.band is not None else run_semi(name) if args.ends is not None else run_local(name) if args.local else run_matrix(name) if args.matrix is not None else
                            run(name) if args.gap_open is None else run_affine(name))
 os.makedirs(os.path.dirname(args.out), exist_ok=True)
 with open(args.out, "w") as f:
