@@ -23,7 +23,10 @@
 // async, nw_score_batch_dual, nw_align_batch_dual; kernels in nw_batch_dual.hip) are the
 // matrix ones with a second (open, extend) piece: the Cost carries it, a worker's column
 // scratch is three columns, a pair's direction bytes are nw_batch_dual_dir_bytes, and the
-// sweep and the walk are that file's.
+// sweep and the walk are that file's.  The two-piece banded entries (nw_score_batch_dual_banded_
+// async, nw_score_batch_dual_banded, nw_align_batch_dual_banded; kernels in nw_batch_dual_
+// banded.hip) are the two-piece ones with a band width: the Cost is both dual and banded, a
+// pair's direction bytes are nw_batch_dual_banded_dir_bytes.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -56,6 +59,7 @@ struct Cost {
     size_t out_bytes() const { return hits() ? sizeof(nw_local_hit) : sizeof(int32_t); }
     int64_t col_words(int64_t max_n2) const { return nw::batch_col_words(max_n2) * (dual ? 3 : affine ? 2 : 1); }
     int64_t dir_bytes(int64_t n1, int64_t n2) const {
+        if (banded && dual) return nw_batch_dual_banded_dir_bytes(n1, n2, band);
         if (banded) return nw_batch_banded_dir_bytes(n1, n2, band);
         if (dual) return nw_batch_dual_dir_bytes(n1, n2);
         return affine ? nw_batch_affine_dir_bytes(n1, n2) : nw_batch_dir_bytes(n1, n2);
@@ -120,6 +124,13 @@ Cost dual_cost(const nw_submat *m, int32_t gap_open, int32_t gap_open2, int32_t 
     c.dual = true;
     c.open2 = gap_open2;
     c.gap2 = gap2;
+    return c;
+}
+
+Cost dual_banded_cost(const nw_submat *m, int32_t gap_open, int32_t gap_open2, int32_t gap2, int32_t band) {
+    Cost c = dual_cost(m, gap_open, gap_open2, gap2);
+    c.banded = true;
+    c.band = band;
     return c;
 }
 
@@ -197,9 +208,10 @@ int params_check(const nw_params *p, int64_t npairs, const Cost &cost) {
     if (npairs < 0 || npairs >= INT32_MAX) return NW_ERR_ARG;
     if (cost.matrix && !valid_submat(cost.mat)) return NW_ERR_ARG;
     if (cost.semi && (cost.ends < 0 || cost.ends > NW_ENDS_OVERLAP)) return NW_ERR_ARG;
-    if (cost.banded && cost.band < 0) return NW_ERR_ARG;
     // piece 2 as piece 1: no positive opening, the extension within nw_params.gap's range
     if (cost.dual && (cost.open2 > 0 || !valid_gap(cost.gap2))) return NW_ERR_ARG;
+    // (after the two-piece refusals; the banded entries have none of those)
+    if (cost.banded && cost.band < 0) return NW_ERR_ARG;
     return NW_OK;
 }
 
@@ -312,6 +324,14 @@ int batch_run(nw_ctx *c, const nw::BatchMatrixArgs &ma, const Cost &cost, bool d
         sa.m.a.b.scores = nullptr;
         sa.ends = cost.ends;
         e = nw::launch_batch_semi(sa, dirs, g, stream);
+    } else if (cost.banded && cost.dual) {
+        nw::BatchDualBandedArgs ba;
+        ba.d.m = ma;
+        ba.d.gap_open2 = cost.open2;
+        ba.d.gap2 = cost.gap2;
+        ba.d.eoff2 = 2 * ma.a.eoff;
+        ba.band = cost.band;
+        e = nw::launch_batch_dual_banded(ba, dirs, g, stream);
     } else if (cost.banded) {
         nw::BatchBandedArgs ba;
         ba.m = ma;
@@ -612,6 +632,11 @@ int align_batch(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, c
             sw.hits = d.scores;
             sw.ends = cost.ends;
             e = nw::launch_batch_semi_walk(sw, nullptr);
+        } else if (cost.banded && cost.dual) {  // five states over the strips' ranges
+            nw::BatchDualBandedWalkArgs bw;
+            bw.w = w;
+            bw.band = cost.band;
+            e = nw::launch_batch_dual_banded_walk(bw, nullptr);
         } else if (cost.banded) {  // the affine walk over the strips' ranges
             nw::BatchBandedWalkArgs bw;
             bw.w = w;
@@ -677,6 +702,11 @@ int64_t nw_batch_banded_dir_bytes(int64_t n1, int64_t n2, int32_t band) {
 
 int64_t nw_batch_dual_dir_bytes(int64_t n1, int64_t n2) {
     const int64_t b = nw_batch_affine_dir_bytes(n1, n2);
+    return b < 0 ? b : 2 * b;
+}
+
+int64_t nw_batch_dual_banded_dir_bytes(int64_t n1, int64_t n2, int32_t band) {
+    const int64_t b = nw_batch_banded_dir_bytes(n1, n2, band);
     return b < 0 ? b : 2 * b;
 }
 
@@ -828,6 +858,29 @@ int nw_align_batch_dual(const int8_t *s1cat, const int64_t *off1, const int8_t *
                         int64_t *n_ops, nw_batch_stats *stats) {
     return align_batch(s1cat, off1, s2cat, off2, npairs, p, dual_cost(m, gap_open, gap_open2, gap2), o, scores, ops,
                        ops_off, n_ops, stats);
+}
+
+int nw_score_batch_dual_banded_async(nw_ctx *c, const int8_t *d_s1cat, const int64_t *d_off1, const int8_t *d_s2cat,
+                                     const int64_t *d_off2, int64_t npairs, int64_t total1, int64_t total2,
+                                     int64_t max_n2, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                                     int32_t gap_open2, int32_t gap2, int32_t band, int32_t *d_scores, void *stream) {
+    return score_batch_async(c, d_s1cat, d_off1, d_s2cat, d_off2, npairs, total1, total2, max_n2, p,
+                             dual_banded_cost(m, gap_open, gap_open2, gap2, band), d_scores, stream);
+}
+
+int nw_score_batch_dual_banded(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                               int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                               int32_t gap_open2, int32_t gap2, int32_t band, int32_t *scores, nw_batch_stats *stats) {
+    return score_batch(s1cat, off1, s2cat, off2, npairs, p, dual_banded_cost(m, gap_open, gap_open2, gap2, band),
+                       scores, stats);
+}
+
+int nw_align_batch_dual_banded(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                               int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                               int32_t gap_open2, int32_t gap2, int32_t band, const nw_batch_opts *o, int32_t *scores,
+                               uint8_t *ops, const int64_t *ops_off, int64_t *n_ops, nw_batch_stats *stats) {
+    return align_batch(s1cat, off1, s2cat, off2, npairs, p, dual_banded_cost(m, gap_open, gap_open2, gap2, band), o,
+                       scores, ops, ops_off, n_ops, stats);
 }
 
 }  // extern "C"

@@ -171,6 +171,22 @@ struct BatchDualArgs {
     int64_t eoff2;
 };
 
+// The two-piece kernels inside a band (nw_batch_dual_banded.hip): the two-piece launch's
+// arguments and the band width w >= 0 of the call, as BatchBandedArgs has it.  The directions
+// kernel writes a byte per cell for the slots of each strip's range alone (four times
+// kBatchDirIter per slot).
+struct BatchDualBandedArgs {
+    BatchDualArgs d;
+    int32_t band;
+};
+
+// Its walk: the two-piece walk over direction blocks that hold only the iterations of each
+// strip's range.
+struct BatchDualBandedWalkArgs {
+    BatchWalkArgs w;
+    int32_t band;
+};
+
 // mapped (perm and at most kMaxPerm distinct column characters) or raw copy of s2cat
 int launch_batch_rows(const uint8_t *d_s2, int64_t total2, int32_t perm, const uint8_t *meta, uint8_t *d_rows,
                       void *stream);
@@ -203,5 +219,9 @@ int launch_batch_banded_walk(const BatchBandedWalkArgs &w, void *stream);
 // per cell, the walk is a machine of five states over a byte per cell
 int launch_batch_dual(const BatchDualArgs &a, bool dirs, int grid, void *stream);
 int launch_batch_dual_walk(const BatchWalkArgs &w, void *stream);
+// the same inside a band: the two-piece cell under the banded ranges, the five-state walk over
+// the slots those ranges leave
+int launch_batch_dual_banded(const BatchDualBandedArgs &a, bool dirs, int grid, void *stream);
+int launch_batch_dual_banded_walk(const BatchDualBandedWalkArgs &w, void *stream);
 
 }  // namespace nw

@@ -2,7 +2,8 @@
 // nw_batch_affine.hip, nw_batch_matrix.hip, nw_batch_local.hip, nw_batch_semi.hip,
 // nw_batch_banded.hip, which runs sweep_tickets and sweep_iter under its own pair loop, and
 // nw_batch_dual.hip, which runs sweep_tickets and ProfileSub under its own pair and iteration
-// loops and finds its cells' direction bytes by dual_dir_byte).
+// loops and finds its cells' direction bytes by dual_dir_byte, and nw_batch_dual_banded.hip,
+// which does the same over the banded ranges and finds them by dual_banded_dir_byte).
 // Private to them: every file compiles its own copy (no relocatable device code), so
 // everything here is in the unnamed namespace.
 //
@@ -434,6 +435,18 @@ constexpr int64_t dual_dir_byte(int64_t iters, int64_t r, int64_t c) {
     const int64_t cj = c - 1;
     const int64_t p = cj >> 8, l = (cj & 255) >> 2, k = cj & 3;
     return ((p * iters * 64 + r + l) * 64 + l) * 4 + k;
+}
+
+// The same in the direction block of a banded pair (nw_batch_dual_banded.hip): a strip holds
+// `slots` iterations (batch_banded_slots), the first of them iteration batch_banded_first(p,
+// dlo): byte k of dword [p][s / 64 - first(p)][s % 64][l].  The slot is clamped, so that no
+// index can leave the pair's block whatever (r, c) is asked for.
+constexpr int64_t dual_banded_dir_byte(int64_t slots, int64_t dlo, int64_t r, int64_t c) {
+    const int64_t cj = c - 1;
+    const int64_t p = cj >> 8, l = (cj & 255) >> 2, k = cj & 3;
+    const int64_t s = r + l;
+    const int64_t slot = min(max((s >> 6) - batch_banded_first(p, dlo), (int64_t)0), slots - 1);
+    return (((p * slots + slot) * 64 + (s & 63)) * 64 + l) * 4 + k;
 }
 
 }  // namespace

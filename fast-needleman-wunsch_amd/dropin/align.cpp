@@ -7,7 +7,7 @@
 //   --mem BYTES / --block-rows K: align in linear memory (nw_align_ckpt) within BYTES
 //   of device memory / in blocks of K rows (a multiple of 64); the output is the same.
 //   --score-only: no alignment, the score from the table-free sweep (nw_score).
-//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only] [--gap-open G] [--matrix FILE] [--local | --ends N | --band W | --gap2 O2,E2]
+//   nw_align --batch LIST [--scheme m,mm,g] [--mem BYTES] [--score-only] [--gap-open G] [--matrix FILE] [--local | --ends N | --band W | --gap2 O2,E2 [--gap2-band W]]
 //   LIST: a text file, one pair "A.bdna B.bdna" per line (paths relative to the
 //   list's directory unless absolute); all pairs are aligned in ONE call
 //   (nw_align_batch; --score-only: nw_score_batch).  stdout: "<ms>\n", then one
@@ -46,6 +46,11 @@
 //   short gaps by the steep piece, long ones by the flat piece (minimap2's -O4,24 -E2,1 is
 //   --scheme 2,-4,-2 --gap-open -4 --gap2 -24,-1).  Substitution as --band's; one "Score:"
 //   line per pair.
+//   --gap2-band W (with --gap2 only, not with --band, --local or --ends; W >= 0): the two-piece
+//   gap cost inside a band (nw_align_batch_dual_banded / nw_score_batch_dual_banded): only
+//   paths that stay within W diagonals of the pair's own count, and a long gap in them is
+//   still priced by the flat piece.  (--gap2 with --band stays an error: --band is the
+//   one-piece entry's option.)
 // Argument and missing-file errors are nw_driver's (exit 1); a device failure is
 // reported on stderr and exits 2.
 #include <chrono>
@@ -171,7 +176,8 @@ static std::string row_text(const std::vector<int8_t> &row) {
 
 // --batch LIST: every pair of the list in one call
 static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bool score_only, const int32_t *gap_open,
-                     const char *matrix, bool local, int ends, int64_t band, const int32_t *gap2) {
+                     const char *matrix, bool local, int ends, int64_t band, const int32_t *gap2,
+                     int64_t gap2_band) {
     nw_submat mat;
     bool listed[256];
     const bool semi = ends >= 0;
@@ -263,6 +269,14 @@ static int run_batch(const char *list, const nw_params &p, int64_t mem_bytes, bo
                         : nw_align_batch_banded(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
                                                 gap_open ? *gap_open : 0, (int32_t)band, &bo, scores.data(),
                                                 ops.data(), ops_off.data(), n_ops.data(), nullptr);
+    else if (dual && gap2_band >= 0)
+        st = score_only
+                 ? nw_score_batch_dual_banded(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
+                                              gap_open ? *gap_open : 0, gap2[0], gap2[1], (int32_t)gap2_band,
+                                              scores.data(), nullptr)
+                 : nw_align_batch_dual_banded(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
+                                              gap_open ? *gap_open : 0, gap2[0], gap2[1], (int32_t)gap2_band, &bo,
+                                              scores.data(), ops.data(), ops_off.data(), n_ops.data(), nullptr);
     else if (dual)
         st = score_only ? nw_score_batch_dual(s1cat.data(), off1.data(), s2cat.data(), off2.data(), npairs, &p, &mat,
                                               gap_open ? *gap_open : 0, gap2[0], gap2[1], scores.data(), nullptr)
@@ -329,6 +343,7 @@ int main(int argc, char **argv) {
     long long band = -1;  // --band W: banded global
     int32_t gap2[2] = {0, 0};  // --gap2 O2,E2: the second piece of the gap cost
     bool dual = false;
+    long long gap2_band = -1;  // --gap2-band W: the two-piece cost inside a band
     for (int a = 1; a < argc; ++a) {
         if (std::strcmp(argv[a], "--scheme") == 0) {
             int m, mm, g;
@@ -384,6 +399,15 @@ int main(int argc, char **argv) {
             }
             band = v;
             ++a;
+        } else if (std::strcmp(argv[a], "--gap2-band") == 0) {
+            long long v = 0;
+            char tail = 0;
+            if (a + 1 >= argc || std::sscanf(argv[a + 1], "%lld%c", &v, &tail) != 1 || v < 0 || v > INT32_MAX) {
+                std::cout << "error: --gap2-band expects a number >= 0 (below 2^31)" << std::endl;
+                return 1;
+            }
+            gap2_band = v;
+            ++a;
         } else if (std::strcmp(argv[a], "--gap2") == 0) {
             int o2 = 0, e2 = 0;
             char tail = 0;
@@ -410,7 +434,7 @@ int main(int argc, char **argv) {
     if (batch != nullptr) {
         if (!pos.empty() || co.block_rows != 0) {
             std::cout << "error: --batch takes the list alone (and --scheme, --mem, --score-only, --gap-open, "
-                         "--matrix, --local, --ends, --band, --gap2)"
+                         "--matrix, --local, --ends, --band, --gap2, --gap2-band)"
                       << std::endl;
             return 1;
         }
@@ -421,6 +445,16 @@ int main(int argc, char **argv) {
         if (band >= 0 && (local || ends >= 0)) {
             std::cout << "error: --band cannot be combined with " << (local ? "--local" : "--ends")
                       << " (the band is built for the global alignment only)" << std::endl;
+            return 1;
+        }
+        if (gap2_band >= 0 && (band >= 0 || local || ends >= 0)) {
+            std::cout << "error: --gap2-band cannot be combined with "
+                      << (band >= 0 ? "--band" : local ? "--local" : "--ends")
+                      << " (it is the band of the two-piece global alignment)" << std::endl;
+            return 1;
+        }
+        if (gap2_band >= 0 && !dual) {
+            std::cout << "error: --gap2-band needs --gap2 (the one-piece band is --band)" << std::endl;
             return 1;
         }
         if (dual && (local || ends >= 0 || band >= 0)) {
@@ -436,7 +470,12 @@ int main(int argc, char **argv) {
             p.mode = NW_MODE_SW;
         }
         return run_batch(batch, p, co.mem_bytes, score_only, affine ? &gap_open : nullptr, matrix, local, ends, band,
-                         dual ? gap2 : nullptr);
+                         dual ? gap2 : nullptr, gap2_band);
+    }
+    if (gap2_band >= 0) {
+        std::cout << "error: --gap2-band needs --batch (the band is built for the batched alignment only)"
+                  << std::endl;
+        return 1;
     }
     if (dual) {
         std::cout << "error: --gap2 needs --batch (the two-piece gap cost is built for the batched alignment only)"

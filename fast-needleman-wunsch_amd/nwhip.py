@@ -52,7 +52,9 @@ EXPORTS = ["nw_params_default", "nw_strerror", "nw_version", "nw_fill", "nw_tabl
            "nw_batch_banded_dir_bytes", "nw_score_batch_banded_async", "nw_score_batch_banded",
            "nw_align_batch_banded",
            "nw_batch_dual_dir_bytes", "nw_score_batch_dual_async", "nw_score_batch_dual", "nw_align_batch_dual",
-           "nw_ops_score_dual"]
+           "nw_ops_score_dual",
+           "nw_batch_dual_banded_dir_bytes", "nw_score_batch_dual_banded_async", "nw_score_batch_dual_banded",
+           "nw_align_batch_dual_banded"]
 IPC_HANDLE_BYTES = 64
 
 
@@ -313,6 +315,20 @@ def lib() -> ctypes.CDLL:
     L.nw_align_batch_dual.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams), _smp,
                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(NwBatchOpts),
                                       _i32p, _u8p, _i64p_, _i64p_, ctypes.POINTER(NwBatchStats)]
+    L.nw_batch_dual_banded_dir_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]
+    L.nw_batch_dual_banded_dir_bytes.restype = ctypes.c_int64
+    L.nw_score_batch_dual_banded_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                   ctypes.c_int64, ctypes.POINTER(NwParams), _smp, ctypes.c_int32,
+                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                   ctypes.c_void_p]
+    L.nw_score_batch_dual_banded.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams),
+                                             _smp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                             _i32p, ctypes.POINTER(NwBatchStats)]
+    L.nw_align_batch_dual_banded.argtypes = [_i8p, _i64p_, _i8p, _i64p_, ctypes.c_int64, ctypes.POINTER(NwParams),
+                                             _smp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.POINTER(NwBatchOpts), _i32p, _u8p, _i64p_, _i64p_,
+                                             ctypes.POINTER(NwBatchStats)]
     L.nw_ops_score_dual.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                     _u8p, ctypes.c_int64, ctypes.POINTER(NwParams), _smp, ctypes.c_int32,
                                     ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
@@ -1048,6 +1064,66 @@ def align_batch_dual(pairs, mat: SubMatrix, gap: int = -2, gap_open: int = -4, g
     return scores[:n], out, stats
 
 
+def batch_dual_banded_dir_bytes(n1: int, n2: int, band: int) -> int:
+    """Direction bytes of one pair in align_batch_dual_banded (nw_batch_dual_banded_dir_bytes): a
+    byte per cell for the iterations of each strip that can touch the band, 2 *
+    batch_banded_dir_bytes(n1, n2, band); batch_dual_dir_bytes(n1, n2) when the band covers the
+    table; 0 for an empty side, -1 for a negative size or band."""
+    return int(lib().nw_batch_dual_banded_dir_bytes(int(n1), int(n2), _band32(band)))
+
+
+def score_batch_dual_banded(pairs, mat: SubMatrix, gap: int = -2, gap_open: int = -4, gap2: int = -1,
+                            gap_open2: int = -24, band: int = 0, waves: int = 0, device: int = -1,
+                            return_stats: bool = False):
+    """score_batch_dual inside a band (nw_score_batch_dual_banded): only paths that stay within
+    `band` diagonals of the pair's own (of 0 .. n2 - n1) count.  A covering band gives
+    score_batch_dual's scores, equal pieces give score_batch_banded's."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    mat.check(s1, s2)
+    n = len(pairs)
+    scores = np.zeros(max(n, 1), np.int32)
+    stats = NwBatchStats()
+    p = params((1, 0, int(gap)), waves, device)
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_score_batch_dual_banded(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p),
+                                          s2.ctypes.data_as(_i8p), off2.ctypes.data_as(i64p), n, ctypes.byref(p),
+                                          ctypes.byref(mat.c), int(gap_open), int(gap_open2), int(gap2),
+                                          _band32(band), scores.ctypes.data_as(_i32p), ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_score_batch_dual_banded")
+    return (scores[:n], stats) if return_stats else scores[:n]
+
+
+def align_batch_dual_banded(pairs, mat: SubMatrix, gap: int = -2, gap_open: int = -4, gap2: int = -1,
+                            gap_open2: int = -24, band: int = 0, mem_bytes: int = 0, waves: int = 0,
+                            device: int = -1):
+    """align_batch_dual inside a band (nw_align_batch_dual_banded): (scores, [ops of pair 0, ..],
+    NwBatchStats); every vertex of a path lies in the band.  stats.dir_bytes counts the
+    iterations of each strip's range alone (batch_dual_banded_dir_bytes)."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    mat.check(s1, s2)
+    n = len(pairs)
+    ops_off = off1 + off2
+    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
+    scores = np.zeros(max(n, 1), np.int32)
+    n_ops = np.zeros(max(n, 1), np.int64)
+    stats = NwBatchStats()
+    p = params((1, 0, int(gap)), waves, device)
+    o = NwBatchOpts(int(mem_bytes))
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    st = lib().nw_align_batch_dual_banded(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p),
+                                          s2.ctypes.data_as(_i8p), off2.ctypes.data_as(i64p), n, ctypes.byref(p),
+                                          ctypes.byref(mat.c), int(gap_open), int(gap_open2), int(gap2),
+                                          _band32(band), ctypes.byref(o), scores.ctypes.data_as(_i32p),
+                                          ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                          ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p),
+                                          ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, "nw_align_batch_dual_banded")
+    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
+    return scores[:n], out, stats
+
+
 def ops_score_dual(s1, s2, ops, mat: SubMatrix, gap: int = -2, gap_open: int = -4, gap2: int = -1,
                    gap_open2: int = -24, begin=(0, 0)) -> int:
     """Score of an alignment's ops under a matrix and the two-piece gap cost (nw_ops_score_dual):
@@ -1630,7 +1706,8 @@ class Context:
         gap_open (an int): affine gap cost, see score_batch_affine (Context.score_batch_affine).
         mat (a SubMatrix): substitution by matrix, see Context.score_batch_matrix.
         band (an int, with mat): inside a band, see Context.score_batch_banded.
-        piece2 ((gap_open2, gap2), with mat): two-piece gap cost, see Context.score_batch_dual."""
+        piece2 ((gap_open2, gap2), with mat): two-piece gap cost, see Context.score_batch_dual;
+        with band as well: inside a band, see Context.score_batch_dual_banded."""
         import torch
         npairs = int(d_off1.numel()) - 1
         assert d_off1.dtype == torch.int64 and d_off2.dtype == torch.int64 and int(d_off2.numel()) == npairs + 1
@@ -1645,7 +1722,11 @@ class Context:
                 ctypes.c_void_p(d_s2cat.data_ptr() if t2 else 0), ctypes.c_void_p(d_off2.data_ptr()), npairs, t1, t2,
                 int(max_n2), ctypes.byref(p))
         tail = (ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(stream.cuda_stream))
-        if mat is not None and piece2 is not None:
+        if mat is not None and piece2 is not None and band is not None:
+            st, what = lib().nw_score_batch_dual_banded_async(*head, ctypes.byref(mat.c), int(gap_open or 0),
+                                                              int(piece2[0]), int(piece2[1]), _band32(band), *tail), \
+                "nw_score_batch_dual_banded_async"
+        elif mat is not None and piece2 is not None:
             st, what = lib().nw_score_batch_dual_async(*head, ctypes.byref(mat.c), int(gap_open or 0),
                                                        int(piece2[0]), int(piece2[1]), *tail), \
                 "nw_score_batch_dual_async"
@@ -1697,6 +1778,18 @@ class Context:
             raise ValueError("Context.score_batch_dual needs a matrix with other= (it cannot check the sequences)")
         return self.score_batch(d_s1cat, d_off1, d_s2cat, d_off2, max_n2, (1, 0, int(gap)), stream, waves, 0,
                                 gap_open=int(gap_open), mat=mat, piece2=(int(gap_open2), int(gap2)))
+
+    def score_batch_dual_banded(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, mat: SubMatrix, gap: int = -2,
+                                gap_open: int = -4, gap2: int = -1, gap_open2: int = -24, band: int = 0,
+                                stream=None, waves: int = 0):
+        """Context.score_batch_dual inside a band of `band` diagonals round each pair's own
+        (nw_score_batch_dual_banded_async, score_batch_dual_banded)."""
+        if mat.other is None and not mat.listed.all():
+            raise ValueError("Context.score_batch_dual_banded needs a matrix with other= (it cannot check the "
+                             "sequences)")
+        return self.score_batch(d_s1cat, d_off1, d_s2cat, d_off2, max_n2, (1, 0, int(gap)), stream, waves, 0,
+                                gap_open=int(gap_open), mat=mat, band=int(band),
+                                piece2=(int(gap_open2), int(gap2)))
 
     def score_batch_local(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, mat: SubMatrix, gap: int = -1,
                           gap_open: int = 0, stream=None, waves: int = 0):

@@ -809,6 +809,60 @@ int nw_align_batch_dual(const int8_t *s1cat, const int64_t *off1, const int8_t *
                         int32_t gap2, const nw_batch_opts *o, int32_t *scores, uint8_t *ops, const int64_t *ops_off,
                         int64_t *n_ops, nw_batch_stats *stats);
 
+/* The two-piece gap cost inside a band ----------------------------------------------
+ * The aligner for long reads: global, banded, concave gap cost, many pairs per call.  The
+ * entries are the two-piece entries' with `int32_t band` after gap2.  The definition is the
+ * conjunction of the two above and nothing else:
+ *   - the recurrence, the boundaries, the walk of five states and its tie-breaks are the
+ *     two-piece entries' (nw_*_batch_dual), word for word;
+ *   - the band is the banded entries' (nw_*_batch_banded): with w = band, dlo = min(0, n2 -
+ *     n1) - w and dhi = max(0, n2 - n1) + w, cell (i, j), 0 <= i <= n2, 0 <= j <= n1, counts iff
+ *     dlo <= i - j <= dhi, boundary cells included; H, E_1, E_2, F_1 and F_2 of a cell outside
+ *     the band are -inf.  score = H[n2][n1].
+ * Equivalently the score is the best two-piece score (the sum of s over the diagonal steps
+ * plus g(k) per maximal run) over the global paths all of whose vertices lie in the band.
+ * Both corners are in the band for every w >= 0, and so is the path "diagonal, then one
+ * run" to any in-band cell: every in-band inner cell is finite.  The walk never leaves the
+ * band: a source or a run is chosen only where its value equals a finite H, and a value that
+ * came from outside the band is -inf.  One long deletion -- what piece 2 exists to price --
+ * lies inside a narrow band, because the band is defined between the table's two corners.
+ * Reductions, byte for byte in scores, ops and n_ops: a covering band (w >= max(n1, n2))
+ * gives nw_*_batch_dual's results; equal pieces, or a piece 2 that is nowhere above piece 1
+ * (go2 <= go1 and ge2 <= ge1), give nw_*_batch_banded's.  The score does not decrease in w.
+ * A pair with an empty side follows the two-piece entries: g(max(n1, n2)) (0 for 0 x 0), ops
+ * all ups or all lefts, whatever the band.  Refusals and their order are the two-piece
+ * entries'; after them NW_ERR_ARG for band < 0; then, per pair, the two-piece entries' range
+ * bound 3*G + (M + A) * (n1 + n2 + 2) < 2^28.  It still holds with cells forced to -inf: its
+ * lower bound on H needs one path with at most two openings that the recurrence can take,
+ * and "diagonal, then one run" is such a path inside the band; the bounds on E_t and F_t are
+ * per step; a forced cell holds no real value, and the kernel adds to its -2^29 at most once
+ * (csrc/nw_batch_dual_banded.hip's header has the argument for piece 2's drift).  The ops are
+ * scored by nw_ops_score_dual.
+ *
+ * nw_batch_dual_banded_dir_bytes: direction bytes of one pair in nw_align_batch_dual_banded,
+ * 2 * nw_batch_banded_dir_bytes(n1, n2, band): a byte per cell for the iterations of each
+ * strip's range alone.  0 when a side is empty, -1 for a negative size or band; equal to
+ * nw_batch_dual_dir_bytes under a covering band, never above it, not decreasing in band.  The
+ * chunking under mem_bytes uses it.  Host only. */
+int64_t nw_batch_dual_banded_dir_bytes(int64_t n1, int64_t n2, int32_t band);
+
+int nw_score_batch_dual_banded_async(nw_ctx *ctx, const int8_t *d_s1cat, const int64_t *d_off1,
+                                     const int8_t *d_s2cat, const int64_t *d_off2, int64_t npairs, int64_t total1,
+                                     int64_t total2, int64_t max_n2, const nw_params *p, const nw_submat *m,
+                                     int32_t gap_open, int32_t gap_open2, int32_t gap2, int32_t band,
+                                     int32_t *d_scores, void *stream);
+
+int nw_score_batch_dual_banded(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                               int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                               int32_t gap_open2, int32_t gap2, int32_t band, int32_t *scores,
+                               nw_batch_stats *stats);
+
+int nw_align_batch_dual_banded(const int8_t *s1cat, const int64_t *off1, const int8_t *s2cat, const int64_t *off2,
+                               int64_t npairs, const nw_params *p, const nw_submat *m, int32_t gap_open,
+                               int32_t gap_open2, int32_t gap2, int32_t band, const nw_batch_opts *o,
+                               int32_t *scores, uint8_t *ops, const int64_t *ops_off, int64_t *n_ops,
+                               nw_batch_stats *stats);
+
 /* Launch-only variant for timing loops: no synchronisation, no readback. */
 int nw_fill_device_async(nw_ctx *ctx, const int8_t *d_s1, int64_t n1,
                          const int8_t *d_s2, int64_t n2, const nw_params *p,

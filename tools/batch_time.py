@@ -57,6 +57,15 @@ library's one-pair path, unchanged by the batch; its scores must equal the batch
                     profiles/batch_dual_time.json.  (A value that starts with a minus sign is
                     written with the equals sign: --gap2=-24,-1.)
 
+  --gap2 O2,E2 --band W [W ..]
+                    the two-piece entries inside a band (nw_score_batch_dual_banded, nw_align_batch_
+                    dual_banded) per width W on --gap2's pairs, matrix and costs.  In the same process,
+                    before them, the unbanded two-piece entries on the SAME pairs (the yardstick: code
+                    the band does not touch) and the ratios, the score kernels' next to the ratio
+                    predicted from the iterations a strip sweeps, masked and plain, each weighted by
+                    the instructions it issues (predict_dual_band).  Writes
+                    profiles/batch_dual_banded_time.json.  --gap2 alone and --band alone are unchanged.
+
 The score kernel's yardstick is the checkpoint sweep's pace on one huge table
 (profiles/ckpt_time.json: 262144^2 in 20.62 ms); `fraction_of_sweep_pace` states it.
 """
@@ -100,7 +109,9 @@ if args.local or args.ends is not None or args.band is not None or args.gap2 is 
 if args.matrix is not None and args.gap_open is None:
     args.gap_open = -11
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "batch_dual_time.json" if args.gap2 is not None else
+    args.out = os.path.join(ROOT, "profiles", "batch_dual_banded_time.json"
+                            if args.gap2 is not None and args.band is not None else
+                            "batch_dual_time.json" if args.gap2 is not None else
                             "batch_banded_time.json" if args.band is not None else
                             "batch_semi_time.json" if args.ends is not None else
                             "batch_local_time.json" if args.local else
@@ -395,6 +406,84 @@ def run_dual(name):
     return e
 
 
+# Instructions a 64-step iteration of the banded two-piece score kernel issues, from its ISA (the
+# narrow form): VALU + v_readlane + v_writelane of the four variants' blocks; the
+# unbanded two-piece kernel's are DUAL_ITER
+DUAL_BANDED_ITER = {("plain", "plain"): 3692 + 384 + 189, ("plain", "edge"): 4769 + 384 + 189,
+                    ("masked", "plain"): 4986 + 384 + 189, ("masked", "edge"): 6048 + 384 + 189}
+
+
+def dual_band_iterations(n1, n2, w):
+    """{(masked / plain, edge / plain): count} of the iterations the banded two-piece sweep runs
+    (the geometry of band_iterations), and {edge / plain: count} of those the unbanded one runs."""
+    dlo = max(min(0, n2 - n1) - w, -n1 - 1024)
+    dhi = min(max(0, n2 - n1) + w, n2 + 1024)
+    iters, nblocks = n2 // 64 + 2, n2 // 64 + 1
+    slots = min(iters, (dhi - dlo + 319 + 63) // 64 + 2)
+    strips = (n1 + 255) // 256
+    edge = lambda it: "edge" if it == 0 or 64 * it + 63 > n2 else "plain"
+    got = {k: 0 for k in DUAL_BANDED_ITER}
+    for p in range(strips):
+        c0 = 256 * p
+        it0 = max(0, (c0 + dlo) >> 6)
+        itl = min(nblocks, ((c0 + 319 + dhi) >> 6) + 1, it0 + slots - 1)
+        for it in range(it0, itl + 1):
+            inside = 64 * it - c0 - 319 >= dlo and 64 * it + 62 - c0 <= dhi
+            got[("plain" if inside else "masked", edge(it))] += 1
+    full = {"edge": 0, "plain": 0}
+    for it in range(iters):
+        full[edge(it)] += strips
+    return got, full
+
+
+def predict_dual_band(pairs, w):
+    """(the banded two-piece score kernel's time over the unbanded one's on the same pairs: every
+    iteration costs the instructions it issues; the iterations: masked, plain, all)."""
+    num = den = 0
+    cnt = {"masked": 0, "plain": 0, "all": 0}
+    for a, b in pairs:
+        got, full = dual_band_iterations(a.size, b.size, w)
+        num += sum(n * DUAL_BANDED_ITER[k] for k, n in got.items())
+        den += sum(n * DUAL_ITER[k] for k, n in full.items())
+        for (m, _), n in got.items():
+            cnt[m] += n
+        cnt["all"] += sum(full.values())
+    return round(num / den, 3), cnt
+
+
+def run_dual_banded(name):
+    go, ge = args.gap_open, -2
+    go2, ge2 = args.gap2
+    letters, mat = make_matrix(20)
+    pairs = make_pairs(name, letters)
+    cells = sum(a.size * b.size for a, b in pairs)
+    e = {"shape": name, "pairs": len(pairs), "cells": int(cells), "gap_open": go, "gap": ge, "gap_open2": go2,
+         "gap2": ge2, "letters": 20,
+         "lengths": "uniform %d..%d" % SHAPES[name][1:] if name == "mixed" else "%d x %d" % SHAPES[name][1:]}
+    dual = dict(gap=ge, gap_open=go, gap2=ge2, gap_open2=go2)
+    gs, ga, glob = time_entries(pairs, cells, lambda p, **kw: nwhip.score_batch_dual(p, mat, **dual, **kw),
+                                lambda p: nwhip.align_batch_dual(p, mat, **dual))
+    e["score_batch_dual"], e["align_batch_dual"] = gs, ga
+    for w in args.band:
+        s, a, sc = time_entries(pairs, cells,
+                                lambda p, **kw: nwhip.score_batch_dual_banded(p, mat, band=w, **dual, **kw),
+                                lambda p: nwhip.align_batch_dual_banded(p, mat, band=w, **dual))
+        assert (sc <= glob).all()   # (a band can only lower a score)
+        (pred, cnt), got = predict_dual_band(pairs, w), round(s["fill_ms"] / gs["fill_ms"], 3)
+        assert a["dir_bytes"] == sum(nwhip.batch_dual_banded_dir_bytes(x.size, y.size, w) for x, y in pairs)
+        e["band_%d" % w] = {
+            "scores_equal_unbanded": int((sc == glob).sum()), "score_batch_dual_banded": s,
+            "align_batch_dual_banded": a, "iterations": cnt,
+            "score_banded_over_dual": got, "predicted_score_banded_over_dual": pred,
+            "explained": bool(abs(got - pred) <= 0.15),
+            "align_fill_banded_over_dual": round(a["fill_ms"] / ga["fill_ms"], 3),
+            "align_fill_walk_banded_over_dual": round(a["fill_walk_ms"] / ga["fill_walk_ms"], 3),
+            "dir_bytes_per_pair": int(a["dir_bytes"] // len(pairs)),
+            "dir_bytes_banded_over_dual": round(a["dir_bytes"] / ga["dir_bytes"], 4)}
+    print(json.dumps(e), flush=True)
+    return e
+
+
 def run(name):
     pairs = make_pairs(name)
     cells = sum(a.size * b.size for a, b in pairs)
@@ -439,7 +528,7 @@ if os.path.exists(args.out):
 rec.update({"device": torch.cuda.get_device_name(0), "library": nwhip.version(), "scheme": list(scheme),
             "reps": args.reps, "sweep_yardstick_gcups": round(SWEEP_GCUPS, 1)})
 for name in (list(SHAPES) if args.shape == "all" else [args.shape]):
-    rec["shapes"][name] = (run_dual(name) if args.gap2 is not None else run_banded(name) if args.band is not None else run_semi(name) if args.ends is not None else run_local(name) if args.local else run_matrix(name) if args.matrix is not None else
+    rec["shapes"][name] = (run_dual_banded(name) if args.gap2 is not None and args.band is not None else run_dual(name) if args.gap2 is not None else run_banded(name) if args.band is not None else run_semi(name) if args.ends is not None else run_local(name) if args.local else run_matrix(name) if args.matrix is not None else
                            run(name) if args.gap_open is None else run_affine(name))
 os.makedirs(os.path.dirname(args.out), exist_ok=True)
 with open(args.out, "w") as f:
