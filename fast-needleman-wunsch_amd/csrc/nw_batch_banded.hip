@@ -50,6 +50,13 @@
 //      Iterations whose 64 steps lie wholly in the band (64it - 256p - 319 >= dlo and 64it
 //    + 62 - 256p <= dhi: wave-uniform, decided like `edge`) run sweep_iter on the
 //    MatrixCell base: the matrix kernel's iteration.
+//    nw_batch_dual_banded.hip takes the arithmetic of points 1 to 3 from BandRange
+//    (nw_batch_dev.h); banded_pair keeps its own text of it: on BandRange the sweeps came out
+//    with the strip's set-up in another order and registers renamed after it (resources the
+//    same), 15 of 16 fill entries were within the parent's spread and the score kernel's fill
+//    of 8000 x 8000 under a covering band measured 16.92 -> 16.98 ms, 1.003 x against a
+//    spread of 0.0025, all five runs above all of the parent's
+//    (profiles/batch_dual_refactor_ab.json).
 //
 // 3. The feed is masked where it is read.  Lane x of the feed of block b holds row 64b +
 //    x of column 256p (strip 0: of the boundary column, H'[r][0] = go, H'[0][0] = 0); it is

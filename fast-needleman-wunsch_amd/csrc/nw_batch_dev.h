@@ -1,19 +1,22 @@
 // nw_batch_dev.h -- device code shared by the batch kernels' files (nw_batch.hip,
 // nw_batch_affine.hip, nw_batch_matrix.hip, nw_batch_local.hip, nw_batch_semi.hip,
 // nw_batch_banded.hip, which runs sweep_tickets and sweep_iter under its own pair loop, and
-// nw_batch_dual.hip, which runs sweep_tickets and ProfileSub under its own pair and iteration
-// loops and finds its cells' direction bytes by dual_dir_byte, and nw_batch_dual_banded.hip,
-// which does the same over the banded ranges and finds them by dual_banded_dir_byte).
-// Private to them: every file compiles its own copy (no relocatable device code), so
-// everything here is in the unnamed namespace.
+// the two two-piece files nw_batch_dual.hip and nw_batch_dual_banded.hip, which run
+// sweep_tickets and ProfileSub under their own pair loops, share their iteration and walk
+// through nw_batch_dual_dev.h and find their cells' direction bytes by dual_dir_byte and
+// dual_banded_dir_byte).  Private to them: every file compiles its own copy (no relocatable
+// device code), so everything here is in the unnamed namespace.
 //
-// For all of them: load_rows, uniform64, claim_ticket.  For the affine family (the last
-// four, which carry H and E from column to column and write 4 direction bits per cell):
-// the index of a cell's direction bits (NW_DIR_NIBBLE), used by the three walks; and, for
+// For all of them: load_rows, uniform64, claim_ticket.  For the affine family (all but the
+// linear file, which carry H and E from column to column): the index of a cell's direction
+// bits (NW_DIR_NIBBLE), used by the three walks over 4 bits per cell; and, for
 // nw_batch_matrix.hip, nw_batch_local.hip and nw_batch_semi.hip, build_profile, ProfileSub
 // and the sweep skeleton -- sweep_tickets, sweep_pair, sweep_iter -- which a file
 // instantiates with its cell policy; for nw_batch_matrix.hip and nw_batch_semi.hip the
-// global cell in the w form (GlobalCell, GlobalSweep, MatrixCell).  The linear kernel
+// global cell in the w form (GlobalCell, GlobalSweep, MatrixCell); for nw_batch_local.hip and
+// nw_batch_semi.hip the order of their candidate cells (before); for a banded pair loop the
+// range of a strip, its "inside" test and the feed's mask (BandRange: nw_batch_dual_banded.hip
+// uses it, nw_batch_banded.hip keeps the text it was measured with).  The linear kernel
 // keeps its own sweep (one value per column, 2 bits per cell, no E and no F) and so does
 // the affine kernel (nw_batch_affine.hip says why).
 #pragma once
@@ -405,6 +408,49 @@ struct MatrixCell : GlobalCell, ProfileSub {
         if constexpr (WIDE) d += bias;
         return d;
     }
+};
+
+// ---- the local and semi-global sweeps: the order of their candidates ----
+
+// a candidate (v, i, j) before the best (bv, bi, bj): score descending, row ascending,
+// column ascending
+__device__ __forceinline__ bool before(int32_t v, int32_t i, int32_t j, int32_t bv, int32_t bi, int32_t bj) {
+    return v > bv || (v == bv && (i < bi || (i == bi && j < bj)));
+}
+
+// ---- the banded sweeps: the range of a strip ----
+
+// What the band leaves of a pair (n1 columns, n2 rows, the call's width) to sweep, and of
+// its strip p once strip(p, lane) was called (nw_batch.h has the geometry, nw_batch_banded.hip's
+// header, point 1, the reasons).  dualb_pair loops over it0 .. itl; banded_pair has the same
+// arithmetic in its own text (its header says why).
+struct BandRange {
+    int32_t dlo, dhi;  // cell (i, j) is in the band iff dlo <= i - j <= dhi
+    uint32_t span;     // dhi - dlo
+    int slots;         // iterations of a strip in the pair's direction block
+    int nblocks;       // ceil((n2 + 1) / 64)
+    int32_t c0;        // the column the strip is fed from
+    int it0, itl;      // the strip's first and last iteration
+    int32_t tb;        // 256p + 5 lane + 1 + dlo: step - tb - k = (the diagonal of the lane's column k) - dlo
+
+    __device__ __forceinline__ BandRange(int32_t n1, int32_t n2, int32_t band)
+        : dlo((int32_t)batch_banded_dlo(n1, n2, band)), dhi((int32_t)batch_banded_dhi(n1, n2, band)),
+          span((uint32_t)(dhi - dlo)), slots((int)batch_banded_slots(n1, n2, band)), nblocks(n2 / 64 + 1) {}
+    __device__ __forceinline__ void strip(int p, int lane) {
+        c0 = p * kCkptCols;
+        it0 = (int)batch_banded_first(p, dlo);
+        // (never beyond the strip's slots: the range is that short by its definition, and a
+        // store past the pair's direction block must be impossible whatever the arithmetic)
+        itl = min(min(nblocks, ((c0 + 319 + dhi) >> 6) + 1), it0 + slots - 1);
+        tb = c0 + 5 * lane + 1 + dlo;
+    }
+    // all 64 steps of iteration `it` lie in the band, on every lane (wave-uniform): its first
+    // step's lane 63, column 3, and its last step's lane 0, column 0
+    __device__ __forceinline__ bool inside(int it) const {
+        return 64 * it - c0 - 319 >= dlo && 64 * it + 62 - c0 <= dhi;
+    }
+    // row `row` of column c0, the feed's, is in the band
+    __device__ __forceinline__ bool in(int32_t row) const { return (uint32_t)(row - c0 - dlo) <= span; }
 };
 
 // ---- the affine family: the direction bits of a cell ----

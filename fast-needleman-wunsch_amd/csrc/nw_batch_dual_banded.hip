@@ -9,13 +9,12 @@
 // points 1 and 3, holds word for word with "H', E1' and E2'" for "H' and E'").  What is new
 // here is the mask.
 //
-// The iteration (dualb_iter) is a second copy of nw_batch_dual.hip's dual_iter with a MASK
-// parameter, not a shared template: that file's kernels are held to the ISA of their parent
-// build, and an iteration moved into nw_batch_dev.h behind a hook is a different inlining
-// unit to the optimiser (the NW_DIR_NIBBLE note there records one such move that changed a
-// register allocation).  MASK = false is that iteration instruction for instruction in
-// source; the wave-uniformly "inside" iterations (64it - 256p - 319 >= dlo and 64it + 62 -
-// 256p <= dhi, nw_batch_banded.hip's test) run it, only the others pay the mask.
+// The iteration is nw_batch_dual_dev.h's dual_iter, shared with nw_batch_dual.hip: this file once
+// kept a second copy for fear that sharing would change that file's kernels, and compiling both
+// ways showed it does not -- the unbanded sweeps call dual_iter with MASK = false and come out
+// instruction for instruction as they did from their own text.  The wave-uniformly "inside"
+// iterations (BandRange::inside, nw_batch_dev.h) run MASK = false here too, only the others pay
+// the mask.
 //
 // The mask.  Per lane t = step - (256p + 5l + 1 + dlo) is the diagonal of the lane's column 0
 // minus dlo, t - k for column k; the cell is in the band iff (uint32)(t - k) <= dhi - dlo.  A
@@ -63,146 +62,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "nw_batch_dev.h"
+#include "nw_batch_dual_dev.h"
 
 namespace nw {
 namespace {
 
-struct DualLane {
-    int32_t u[C];   // H' of the lane's current row, column k
-    int32_t f1[C];  // F1' of the lane's current row, column k
-    int32_t f2[C];  // F2'
-    int32_t e1;     // E1' of the lane's current row, last column
-    int32_t e2;     // E2'
-    int32_t dg;     // H'_diag of column 0 for the next step
-    int32_t fvh, fv1, fv2;     // feed: lane x holds H' / E1' / E2' of the left strip's right column at row 64it + x
-    int32_t acch, acc1, acc2;  // right column gathered: lane x holds row 64(it-1) + x
-};
-
-// what a launch's costs are to the cell
-struct DualCost {
-    int32_t go1, go2;
-    int32_t dge;   // ge2 - ge1
-    int32_t bias;  // WIDE: -2 ge1
-    // H' of the boundary cell k columns (or rows) from the corner, k >= 1
-    __device__ __forceinline__ int32_t boundary(int32_t k) const {
-        return max(go1, (int32_t)((uint32_t)go2 + (uint32_t)k * (uint32_t)dge));
-    }
-};
-
-// 64 steps of iteration `it` (steps 64it + u): lane l computes row 64it + u - l.
-//   EDGE : some lane's row is outside 1..n2 in this iteration (it holds its cells)
-//   MASK : some cell of this iteration may lie outside the band: tb = 256p + 5 lane + 1 + dlo
-//          (step - tb - k = the cell's diagonal - dlo), span = dhi - dlo
-//   colw : where H' of the right column of block it - 1 goes, E1' eoff and E2' eoff2 words
-//          behind it (NULL: it has no reader)
-//   dq   : DIRS: this lane's dword of the iteration's first step
-template <bool WIDE, bool EDGE, bool MASK, bool DIRS>
-__device__ __forceinline__ void dualb_iter(int it, const u32x4 (&pk)[4], int32_t n2, const DualCost &K, DualLane &S,
-                                           ProfileSub &P, int32_t tb, uint32_t span, int32_t *colw, int64_t eoff,
-                                           int64_t eoff2, uint32_t *dq, int lane) {
-    int32_t rr = 64 * it - lane - 1;  // EDGE: row of this lane before the step
-    int32_t tt = 64 * it - tb - 1;    // MASK: column 0's diagonal - dlo before the step
-    P.iter_begin(pk);
-    static_for<0, 16>([&](auto gc) {
-        constexpr int gi = decltype(gc)::value;
-        P.template group_begin<gi>(pk);
-        static_for<0, 4>([&](auto qc) {
-            constexpr int q = decltype(qc)::value;
-            constexpr int u = 4 * gi + q;
-            const int32_t lfh = __builtin_amdgcn_readlane(S.fvh, u);
-            const int32_t lf1 = __builtin_amdgcn_readlane(S.fv1, u);
-            const int32_t lf2 = __builtin_amdgcn_readlane(S.fv2, u);
-            int32_t left = __builtin_amdgcn_update_dpp(lfh, S.u[C - 1], 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
-            int32_t el1 = __builtin_amdgcn_update_dpp(lf1, S.e1, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
-            int32_t el2 = __builtin_amdgcn_update_dpp(lf2, S.e2, 0x138 /*wave_shr:1*/, 0xF, 0xF, false);
-            int32_t diag = S.dg;
-            S.dg = left;
-            bool act = true;
-            if constexpr (EDGE) {
-                rr += 1;
-                asm volatile("" : "+v"(rr));  // keep the activity test in the loop
-                act = rr >= 1 && rr <= n2;
-            }
-            if constexpr (MASK) {
-                tt += 1;
-                asm volatile("" : "+v"(tt));  // (one counter, not 64 constants)
-            }
-            uint32_t dw = 0;  // DIRS: byte k = column k's cell of this step
-            static_for<0, C>([&](auto kc) {
-                constexpr int k = decltype(kc)::value;
-                int32_t d = diag + P.template score_byte<q, k>();
-                if constexpr (WIDE) d += K.bias;
-                const int32_t up = S.u[k];
-                const int32_t fo1 = up + K.go1, eo1 = left + K.go1;  // a run opened from H'
-                const int32_t fo2 = up + K.go2, eo2 = left + K.go2;
-                const int32_t f1 = max(S.f1[k], fo1);
-                const int32_t e1 = max(el1, eo1);
-                int32_t f2 = max(S.f2[k], fo2) + K.dge;
-                int32_t e2 = max(el2, eo2) + K.dge;
-                // H' = max(H'_diag + s - 2 ge1, F1', E1', F2', E2')
-                int32_t x = max(max(max(d, f1), e1), max(f2, e2));
-                if constexpr (DIRS) {
-                    uint32_t code = x == d ? 0u : x == f1 ? 1u : x == e1 ? 2u : x == f2 ? 3u : 4u;
-                    code |= el1 > eo1 ? 8u : 0u;
-                    code |= S.f1[k] > fo1 ? 16u : 0u;
-                    code |= el2 > eo2 ? 32u : 0u;
-                    code |= S.f2[k] > fo2 ? 64u : 0u;
-                    dw |= code << (8 * k);
-                }
-                if constexpr (MASK) {
-                    // outside the band: H', E2' and F2' are minus infinity (the header)
-                    const bool out = (uint32_t)(tt - k) > span;
-                    x = out ? kNegInf : x;
-                    e2 = out ? kNegInf : e2;
-                    f2 = out ? kNegInf : f2;
-                }
-                diag = up;
-                if constexpr (EDGE) {
-                    x = act ? x : up;
-                    S.f1[k] = act ? f1 : S.f1[k];
-                    S.f2[k] = act ? f2 : S.f2[k];
-                } else {
-                    S.f1[k] = f1;
-                    S.f2[k] = f2;
-                }
-                S.u[k] = x;
-                left = x;
-                el1 = e1;
-                el2 = e2;
-            });
-            if constexpr (EDGE) {
-                S.e1 = act ? el1 : S.e1;
-                S.e2 = act ? el2 : S.e2;
-            } else {
-                S.e1 = el1;
-                S.e2 = el2;
-            }
-            // lane 63 is on row 64(it-1) + u + 1: into lane (u + 1) % 64 of the gathers
-            const int32_t rvh = __builtin_amdgcn_readlane(S.u[C - 1], 63);
-            const int32_t rv1 = __builtin_amdgcn_readlane(S.e1, 63);
-            const int32_t rv2 = __builtin_amdgcn_readlane(S.e2, 63);
-            if constexpr (u == 63) {
-                // rows 64(it-1) .. + 63 are gathered (lane 0 since the step before this
-                // iteration): out, before lane 0 takes row 64it
-                if (colw != nullptr) {
-                    colw[lane] = S.acch;
-                    colw[eoff + lane] = S.acc1;
-                    colw[eoff2 + lane] = S.acc2;
-                }
-            }
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(S.acch) : "s"(rvh), "i"((u + 1) & 63));
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(S.acc1) : "s"(rv1), "i"((u + 1) & 63));
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(S.acc2) : "s"(rv2), "i"((u + 1) & 63));
-            if constexpr (DIRS) dq[u * kWave] = dw;
-        });
-    });
-}
-
 // One pair (n1, n2 >= 1) by this wave: nw_batch_dual.hip's dual_pair under nw_batch_banded.hip's
-// ranges.  s1: the pair's column characters; rowb[y] = row y's letter; col: the worker's column
-// scratch (H' at col[row], E1' at col[eoff + row], E2' at col[eoff2 + row]); dirs: DIRS: this
-// lane's dword of the pair's first slot.
+// ranges (BandRange).  s1: the pair's column characters; rowb[y] = row y's letter; col: the
+// worker's column scratch (H' at col[row], E1' at col[eoff + row], E2' at col[eoff2 + row]);
+// dirs: DIRS: this lane's dword of the pair's first slot.
 template <bool WIDE, bool DIRS>
 __device__ __forceinline__ void dualb_pair(const BatchDualBandedArgs &BA, uint32_t *pl, const uint8_t *__restrict__ s1,
                                            int32_t n1, const uint8_t *__restrict__ rowb, int32_t n2,
@@ -214,26 +82,14 @@ __device__ __forceinline__ void dualb_pair(const BatchDualBandedArgs &BA, uint32
     const DualCost K{DA.m.a.gap_open, DA.gap_open2, DA.gap2 - ge1, -2 * ge1};
     const int64_t eoff = DA.m.a.eoff, eoff2 = DA.eoff2;
     const int nstrips = (n1 + kCkptCols - 1) / kCkptCols;
-    const int nblocks = n2 / 64 + 1;  // ceil((n2 + 1) / 64)
-    const int lastb = nblocks - 1;
-    const int32_t dlo = (int32_t)batch_banded_dlo(n1, n2, BA.band);
-    const int32_t dhi = (int32_t)batch_banded_dhi(n1, n2, BA.band);
-    const int slots = (int)batch_banded_slots(n1, n2, BA.band);
-    const uint32_t span = (uint32_t)(dhi - dlo);
+    BandRange R(n1, n2, BA.band);
+    const int nblocks = R.nblocks, lastb = nblocks - 1;
     ProfileSub P{pl};
 
     for (int p = 0; p < nstrips; ++p) {
-        const int32_t c0 = p * kCkptCols;      // the column the strip is fed from
-        const int32_t cl = 1 + c0 + C * lane;  // first column of this lane
-        const int it0 = (int)batch_banded_first(p, dlo);
-        // (never beyond the strip's slots: the range is that short by its definition, and a
-        // store past the pair's direction block must be impossible whatever the arithmetic)
-        const int itl = min(min(nblocks, ((c0 + 319 + dhi) >> 6) + 1), it0 + slots - 1);
-        const int32_t tb = c0 + 5 * lane + 1 + dlo;
-        const int32_t fb = lane - c0 - dlo;    // 64b + fb = (row 64b + lane of column c0)'s diagonal - dlo
-        // iterations in_lo .. in_hi lie wholly in the band: 64it - c0 - 319 >= dlo and 64it + 62 - c0
-        // <= dhi (floor divisions: both numerators may be negative)
-        const int in_lo = (c0 + 319 + dlo + 63) >> 6, in_hi = (dhi + c0 - 62) >> 6;
+        R.strip(p, lane);
+        const int32_t cl = 1 + R.c0 + C * lane;  // first column of this lane
+        const int it0 = R.it0;
         DualLane S;
         if (it0 > 0) {
             // every cell before the range is above the band
@@ -243,7 +99,7 @@ __device__ __forceinline__ void dualb_pair(const BatchDualBandedArgs &BA, uint32
         } else {
 #pragma unroll
             for (int k = 0; k < C; ++k) {
-                S.u[k] = (cl + k <= -dlo) ? K.boundary(cl + k) : kNegInf;  // H'[0][c]: in the band iff -c >= dlo
+                S.u[k] = (cl + k <= -R.dlo) ? K.boundary(cl + k) : kNegInf;  // H'[0][c]: in the band iff -c >= dlo
                 S.f1[k] = S.f2[k] = kNegInf;                               // Ft'[0][c]
             }
             S.dg = 0;  // (replaced by H'[0][cl - 1] at the lane's row-0 step, before a cell reads it)
@@ -265,7 +121,7 @@ __device__ __forceinline__ void dualb_pair(const BatchDualBandedArgs &BA, uint32
                 e1 = col[eoff + row];
                 e2 = col[eoff2 + row];
             }
-            const bool in = (uint32_t)(64 * b + fb) <= span;
+            const bool in = R.in(row);
             h = in ? h : kNegInf;
             e1 = in ? e1 : kNegInf;
             e2 = in ? e2 : kNegInf;
@@ -278,8 +134,8 @@ __device__ __forceinline__ void dualb_pair(const BatchDualBandedArgs &BA, uint32
         feed(it0, fnh, fn1, fn2);  // (it0 <= lastb: 256p + dlo < n2)
         // DIRS: this lane's dword of slot it - it0 of strip p, one slot further per iteration
         uint32_t *dq = nullptr;
-        if constexpr (DIRS) dq = dirs + (int64_t)p * slots * (64 * kWave);
-        for (int it = it0; it <= itl; ++it) {
+        if constexpr (DIRS) dq = dirs + (int64_t)p * R.slots * (64 * kWave);
+        for (int it = it0; it <= R.itl; ++it) {
             if (it < nblocks) {
                 S.fvh = fnh;
                 S.fv1 = fn1;
@@ -288,18 +144,21 @@ __device__ __forceinline__ void dualb_pair(const BatchDualBandedArgs &BA, uint32
             feed(min(it + 1, lastb), fnh, fn1, fn2);
             load_rows(rowb, min(it + 1, nblocks), lane, pkn);
             const bool edge = it == 0 || 64 * it + 63 > n2;
-            const bool inside = it >= in_lo && it <= in_hi;
             int32_t *colw = (pub && it > it0) ? col + 64 * (it - 1) : nullptr;
-            if (inside) {
+            if (R.inside(it)) {
                 if (edge)
-                    dualb_iter<WIDE, true, false, DIRS>(it, pkc, n2, K, S, P, tb, span, colw, eoff, eoff2, dq, lane);
+                    dual_iter<WIDE, true, false, DIRS>(it, pkc, n2, K, S, P, R.tb, R.span, colw, eoff, eoff2, dq,
+                                                       lane);
                 else
-                    dualb_iter<WIDE, false, false, DIRS>(it, pkc, n2, K, S, P, tb, span, colw, eoff, eoff2, dq, lane);
+                    dual_iter<WIDE, false, false, DIRS>(it, pkc, n2, K, S, P, R.tb, R.span, colw, eoff, eoff2, dq,
+                                                        lane);
             } else {
                 if (edge)
-                    dualb_iter<WIDE, true, true, DIRS>(it, pkc, n2, K, S, P, tb, span, colw, eoff, eoff2, dq, lane);
+                    dual_iter<WIDE, true, true, DIRS>(it, pkc, n2, K, S, P, R.tb, R.span, colw, eoff, eoff2, dq,
+                                                      lane);
                 else
-                    dualb_iter<WIDE, false, true, DIRS>(it, pkc, n2, K, S, P, tb, span, colw, eoff, eoff2, dq, lane);
+                    dual_iter<WIDE, false, true, DIRS>(it, pkc, n2, K, S, P, R.tb, R.span, colw, eoff, eoff2, dq,
+                                                       lane);
             }
 #pragma unroll
             for (int h = 0; h < 4; ++h) pkc[h] = pkn[h];
@@ -314,21 +173,10 @@ __device__ __forceinline__ void dualb_pair(const BatchDualBandedArgs &BA, uint32
     }
 }
 
-// What the ticket loop below asks of a kernel: sweep_tickets' interface (nw_batch_dev.h).
-struct DualBandedSweep {
+// What the ticket loop below asks of a kernel: sweep_tickets' interface (nw_batch_dev.h),
+// DualSweepBase over the launch's two-piece part and the sweep in its wide or narrow form.
+struct DualBandedSweep : DualSweepBase {
     const BatchDualBandedArgs &BA;
-    uint32_t *pl;  // this lane's dword of profile row 0
-    __device__ __forceinline__ const BatchAffineArgs &affine() const { return BA.d.m.a; }
-    __device__ __forceinline__ int32_t *result(int pair) const { return BA.d.m.a.b.scores + pair; }
-    // not a pair this launch was sized for: the column scratch would not hold it
-    __device__ __forceinline__ void refused(int32_t *score, int lane) const {
-        if (lane == 0) *score = INT32_MIN;
-    }
-    // no cells: the corner of the boundary, one gap of the cheaper piece (none for 0 x 0)
-    __device__ __forceinline__ void empty(int32_t *score, int32_t n, int lane) const {
-        if (lane == 0)
-            *score = n > 0 ? max(BA.d.m.a.gap_open + BA.d.m.a.b.gap * n, BA.d.gap_open2 + BA.d.gap2 * n) : 0;
-    }
     template <bool DIRS>
     __device__ __forceinline__ void pair(int32_t *out, const uint8_t *s1, int32_t n1, const uint8_t *rowb, int32_t n2,
                                          int32_t *col, uint32_t *dirs, int lane) const {
@@ -354,7 +202,7 @@ __global__ __launch_bounds__(64) void nw_batch_dual_banded_sweep(BatchDualBanded
         auto kp = __builtin_amdgcn_kernarg_segment_ptr();  // (a pointer to constant address space)
         asm volatile("" : "+s"(kp));  // (no load of an argument moves above this point)
         const BatchDualBandedArgs &BA = *(const BatchDualBandedArgs *)kp;
-        const DualBandedSweep mode{BA, prof + lane};
+        const DualBandedSweep mode{{BA.d, prof + lane}, BA};
         const BatchArgs &A = BA.d.m.a.b;
         const int t = __builtin_amdgcn_readfirstlane(claim_ticket(A.ticket));  // (a call returns in a vector register)
         if (t >= A.npairs) break;
@@ -381,7 +229,7 @@ __global__ __launch_bounds__(64) void nw_batch_dual_banded_sweep(BatchDualBanded
 // The walk of ticket t's pair from (n2, n1) to (0, 0): nw_batch_dual_walk (its header has the
 // machine of five states) over the banded direction block.  It reads in-band cells only (the
 // header); dual_banded_dir_byte clamps the slot all the same, so that no read can leave the
-// pair's block.
+// pair's block.  (A second text, not a shared body: nw_batch_dual.hip's walk has the measurement.)
 __global__ __launch_bounds__(64) void nw_batch_dual_banded_walk(BatchDualBandedWalkArgs B) {
     const BatchWalkArgs &W = B.w;
     const int t = blockIdx.x * 64 + threadIdx.x;

@@ -45,12 +45,6 @@
 namespace nw {
 namespace {
 
-// a candidate (v, i, j) before the best (bv, bi, bj): score descending, row ascending,
-// column ascending
-__device__ __forceinline__ bool before(int32_t v, int32_t i, int32_t j, int32_t bv, int32_t bi, int32_t bj) {
-    return v > bv || (v == bv && (i < bi || (i == bi && j < bj)));
-}
-
 struct LocalCell : GotohLane, ProfileSub {
     const BatchMatrixArgs &MA;
     int32_t ge, goe;  // goe: go + ge

@@ -47,12 +47,6 @@ namespace {
 
 constexpr int32_t kEndsS1Begin = 1, kEndsS1End = 2, kEndsS2Begin = 4, kEndsS2End = 8;  // NW_ENDS_*
 
-// a candidate (v, i, j) before the best (bv, bi, bj): score descending, row ascending,
-// column ascending
-__device__ __forceinline__ bool before(int32_t v, int32_t i, int32_t j, int32_t bv, int32_t bi, int32_t bj) {
-    return v > bv || (v == bv && (i < bi || (i == bi && j < bj)));
-}
-
 template <bool WIDE, bool COL>
 struct SemiCell : MatrixCell<WIDE> {
     using Base = MatrixCell<WIDE>;

@@ -180,6 +180,8 @@ class NwError(RuntimeError):
 _lib = None
 _i8p = ctypes.POINTER(ctypes.c_int8)
 _i32p = ctypes.POINTER(ctypes.c_int32)
+_i64p = ctypes.POINTER(ctypes.c_int64)
+_u8p = ctypes.POINTER(ctypes.c_uint8)
 
 
 def lib() -> ctypes.CDLL:
@@ -207,7 +209,6 @@ def lib() -> ctypes.CDLL:
     L.nw_fill.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.POINTER(NwParams),
                           _i32p, ctypes.POINTER(NwResult)]
     L.nw_fill_emb.argtypes = L.nw_fill.argtypes
-    _u8p = ctypes.POINTER(ctypes.c_uint8)
     L.nw_sw_align.argtypes = [_i8p, ctypes.c_int64, _i8p, ctypes.c_int64, ctypes.POINTER(NwParams), _u8p,
                               ctypes.c_int64, ctypes.POINTER(NwAlignment)]
     L.nw_sw_traceback.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
@@ -388,7 +389,6 @@ def lib() -> ctypes.CDLL:
     L.nw_auto_shape.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     L.nw_auto_shape.restype = None
-    _i64p = ctypes.POINTER(ctypes.c_int64)
     L.nw_colband_layout.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                     ctypes.POINTER(NwParams), _i64p, _i64p, _i64p, _i64p]
     L.nw_feed_bytes.argtypes = [ctypes.c_int64]
@@ -566,22 +566,60 @@ def batch_csr(pairs):
     return (np.ascontiguousarray(cat1, dtype=np.int8), off1, np.ascontiguousarray(cat2, dtype=np.int8), off2)
 
 
+def _batch_result(n: int, hits: bool):
+    """The result array of a batched call, int32 scores or LOCAL_HIT_DTYPE hits, and its pointer."""
+    res = np.zeros(max(n, 1), LOCAL_HIT_DTYPE if hits else np.int32)
+    return res, res.ctypes.data_as(ctypes.POINTER(NwLocalHit) if hits else _i32p)
+
+
+def _score_batch_call(entry: str, pairs, p: NwParams, extra=(), mat=None, hits: bool = False,
+                      return_stats: bool = False):
+    """One synchronous score call: the C entry `entry` on `pairs` under `p`, with `extra` (after
+    the matrix, when `mat` is given: the sequences are checked against it) between the params and
+    the results; `hits`: nw_local_hit records, not int32 scores."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    if mat is not None:
+        mat.check(s1, s2)
+        extra = (ctypes.byref(mat.c), *extra)
+    n = len(pairs)
+    res, resp = _batch_result(n, hits)
+    stats = NwBatchStats()
+    st = getattr(lib(), entry)(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(_i64p), s2.ctypes.data_as(_i8p),
+                               off2.ctypes.data_as(_i64p), n, ctypes.byref(p), *extra, resp, ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, entry)
+    return (res[:n], stats) if return_stats else res[:n]
+
+
+def _align_batch_call(entry: str, pairs, p: NwParams, mem_bytes: int, extra=(), mat=None, hits: bool = False):
+    """One synchronous align call, as _score_batch_call: (results, [ops of pair 0, ..], NwBatchStats)."""
+    s1, off1, s2, off2 = batch_csr(pairs)
+    if mat is not None:
+        mat.check(s1, s2)
+        extra = (ctypes.byref(mat.c), *extra)
+    n = len(pairs)
+    ops_off = off1 + off2
+    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
+    res, resp = _batch_result(n, hits)
+    n_ops = np.zeros(max(n, 1), np.int64)
+    stats = NwBatchStats()
+    o = NwBatchOpts(int(mem_bytes))
+    st = getattr(lib(), entry)(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(_i64p), s2.ctypes.data_as(_i8p),
+                               off2.ctypes.data_as(_i64p), n, ctypes.byref(p), *extra, ctypes.byref(o), resp,
+                               ops.ctypes.data_as(_u8p), ops_off.ctypes.data_as(_i64p), n_ops.ctypes.data_as(_i64p),
+                               ctypes.byref(stats))
+    if st != NW_OK:
+        raise NwError(st, entry)
+    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
+    return res[:n], out, stats
+
+
 def score_batch(pairs, scheme=(1, 0, -1), waves: int = 0, device: int = -1, flags: int = 0,
                 return_stats: bool = False):
     """Scores of many (s1, s2) pairs in one call (nw_score_batch): an int32 array, the
     score of pair i at index i (and the NwBatchStats with return_stats)."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    n = len(pairs)
-    scores = np.zeros(max(n, 1), np.int32)
-    stats = NwBatchStats()
-    p = params(scheme, waves, device, flags=flags)
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_score_batch(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                              off2.ctypes.data_as(i64p), n, ctypes.byref(p), scores.ctypes.data_as(_i32p),
-                              ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_score_batch")
-    return (scores[:n], stats) if return_stats else scores[:n]
+    return _score_batch_call("nw_score_batch", pairs, params(scheme, waves, device, flags=flags),
+                             return_stats=return_stats)
 
 
 def align_batch(pairs, scheme=(1, 0, -1), mem_bytes: int = 0, waves: int = 0, device: int = -1, flags: int = 0):
@@ -589,24 +627,7 @@ def align_batch(pairs, scheme=(1, 0, -1), mem_bytes: int = 0, waves: int = 0, de
     pair 0, ops of pair 1, ..], NwBatchStats), each ops a uint8 array in path order (0, 0)
     -> (n2, n1) (0 diag, 1 up, 2 left), byte-identical to align's.  mem_bytes: the device
     budget the chunks fit (0 = 80 % of the free device memory)."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    n = len(pairs)
-    ops_off = off1 + off2
-    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
-    scores = np.zeros(max(n, 1), np.int32)
-    n_ops = np.zeros(max(n, 1), np.int64)
-    stats = NwBatchStats()
-    p = params(scheme, waves, device, flags=flags)
-    o = NwBatchOpts(int(mem_bytes))
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_align_batch(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                              off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(o),
-                              scores.ctypes.data_as(_i32p), ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                              ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_align_batch")
-    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
-    return scores[:n], out, stats
+    return _align_batch_call("nw_align_batch", pairs, params(scheme, waves, device, flags=flags), mem_bytes)
 
 
 def batch_affine_dir_bytes(n1: int, n2: int) -> int:
@@ -619,43 +640,16 @@ def score_batch_affine(pairs, scheme=(1, 0, -1), gap_open: int = 0, waves: int =
                        flags: int = 0, return_stats: bool = False):
     """score_batch under affine gap cost (nw_score_batch_affine): a run of L ups or of L
     lefts costs gap_open + L * scheme[2]."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    n = len(pairs)
-    scores = np.zeros(max(n, 1), np.int32)
-    stats = NwBatchStats()
-    p = params(scheme, waves, device, flags=flags)
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_score_batch_affine(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                                     off2.ctypes.data_as(i64p), n, ctypes.byref(p), int(gap_open),
-                                     scores.ctypes.data_as(_i32p), ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_score_batch_affine")
-    return (scores[:n], stats) if return_stats else scores[:n]
+    return _score_batch_call("nw_score_batch_affine", pairs, params(scheme, waves, device, flags=flags),
+                             (int(gap_open),), return_stats=return_stats)
 
 
 def align_batch_affine(pairs, scheme=(1, 0, -1), gap_open: int = 0, mem_bytes: int = 0, waves: int = 0,
                        device: int = -1, flags: int = 0):
     """align_batch under affine gap cost (nw_align_batch_affine): (scores, [ops of pair 0,
     ..], NwBatchStats), the ops the three-state walk include/nw_hip.h defines."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    n = len(pairs)
-    ops_off = off1 + off2
-    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
-    scores = np.zeros(max(n, 1), np.int32)
-    n_ops = np.zeros(max(n, 1), np.int64)
-    stats = NwBatchStats()
-    p = params(scheme, waves, device, flags=flags)
-    o = NwBatchOpts(int(mem_bytes))
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_align_batch_affine(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                                     off2.ctypes.data_as(i64p), n, ctypes.byref(p), int(gap_open), ctypes.byref(o),
-                                     scores.ctypes.data_as(_i32p),
-                                     ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                     ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_align_batch_affine")
-    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
-    return scores[:n], out, stats
+    return _align_batch_call("nw_align_batch_affine", pairs, params(scheme, waves, device, flags=flags), mem_bytes,
+                             (int(gap_open),))
 
 
 def ops_score_affine(s1, s2, ops, scheme=(1, 0, -1), gap_open: int = 0, begin=(0, 0)) -> int:
@@ -804,49 +798,26 @@ class SubMatrix:
         return cls(letters, np.array([rows[b] for b in letters], np.int64), other)
 
 
+def _needs_other(mat: SubMatrix, who: str) -> None:
+    """The calls on device tensors do not look at the sequences: the matrix must cover every byte."""
+    if mat.other is None and not mat.listed.all():
+        raise ValueError(who + " needs a matrix with other= (it cannot check the sequences)")
+
+
 def score_batch_matrix(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, waves: int = 0, device: int = -1,
                        return_stats: bool = False):
     """score_batch_affine with substitution by matrix (nw_score_batch_matrix): s(s1 letter,
     s2 letter) from `mat`, a run of L ups or of L lefts costs gap_open + L * gap."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    mat.check(s1, s2)
-    n = len(pairs)
-    scores = np.zeros(max(n, 1), np.int32)
-    stats = NwBatchStats()
-    p = params((1, 0, int(gap)), waves, device)
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_score_batch_matrix(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                                     off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
-                                     int(gap_open), scores.ctypes.data_as(_i32p), ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_score_batch_matrix")
-    return (scores[:n], stats) if return_stats else scores[:n]
+    return _score_batch_call("nw_score_batch_matrix", pairs, params((1, 0, int(gap)), waves, device),
+                             (int(gap_open),), mat, return_stats=return_stats)
 
 
 def align_batch_matrix(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, mem_bytes: int = 0, waves: int = 0,
                        device: int = -1):
     """align_batch_affine with substitution by matrix (nw_align_batch_matrix): (scores, [ops
     of pair 0, ..], NwBatchStats)."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    mat.check(s1, s2)
-    n = len(pairs)
-    ops_off = off1 + off2
-    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
-    scores = np.zeros(max(n, 1), np.int32)
-    n_ops = np.zeros(max(n, 1), np.int64)
-    stats = NwBatchStats()
-    p = params((1, 0, int(gap)), waves, device)
-    o = NwBatchOpts(int(mem_bytes))
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_align_batch_matrix(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                                     off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
-                                     int(gap_open), ctypes.byref(o), scores.ctypes.data_as(_i32p),
-                                     ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                     ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_align_batch_matrix")
-    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
-    return scores[:n], out, stats
+    return _align_batch_call("nw_align_batch_matrix", pairs, params((1, 0, int(gap)), waves, device), mem_bytes,
+                             (int(gap_open),), mat)
 
 
 def score_batch_local(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, waves: int = 0, device: int = -1,
@@ -855,20 +826,8 @@ def score_batch_local(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, w
     gap cost with substitution by `mat`.  Returns a LOCAL_HIT_DTYPE array, one record per
     pair: score, end_i, end_j (the first row-major maximum; (0, 0) when the score is 0)
     and begin_i = begin_j = -1 (the score entry finds no begin cell)."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    mat.check(s1, s2)
-    n = len(pairs)
-    hits = np.zeros(max(n, 1), LOCAL_HIT_DTYPE)
-    stats = NwBatchStats()
-    p = params((1, 0, int(gap)), waves, device, mode=MODE_SW)
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_score_batch_local(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                                    off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
-                                    int(gap_open), hits.ctypes.data_as(ctypes.POINTER(NwLocalHit)),
-                                    ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_score_batch_local")
-    return (hits[:n], stats) if return_stats else hits[:n]
+    return _score_batch_call("nw_score_batch_local", pairs, params((1, 0, int(gap)), waves, device, mode=MODE_SW),
+                             (int(gap_open),), mat, hits=True, return_stats=return_stats)
 
 
 def align_batch_local(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, mem_bytes: int = 0, waves: int = 0,
@@ -876,26 +835,8 @@ def align_batch_local(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, m
     """Batched local alignments (nw_align_batch_local): (hits, [ops of pair 0, ..],
     NwBatchStats).  hits as score_batch_local with the begin cells filled in; a pair's ops
     (0 diag, 1 up, 2 left) lead from its begin cell to its end cell."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    mat.check(s1, s2)
-    n = len(pairs)
-    ops_off = off1 + off2
-    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
-    hits = np.zeros(max(n, 1), LOCAL_HIT_DTYPE)
-    n_ops = np.zeros(max(n, 1), np.int64)
-    stats = NwBatchStats()
-    p = params((1, 0, int(gap)), waves, device, mode=MODE_SW)
-    o = NwBatchOpts(int(mem_bytes))
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_align_batch_local(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                                    off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
-                                    int(gap_open), ctypes.byref(o), hits.ctypes.data_as(ctypes.POINTER(NwLocalHit)),
-                                    ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                    ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_align_batch_local")
-    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
-    return hits[:n], out, stats
+    return _align_batch_call("nw_align_batch_local", pairs, params((1, 0, int(gap)), waves, device, mode=MODE_SW),
+                             mem_bytes, (int(gap_open),), mat, hits=True)
 
 
 def score_batch_semi(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, ends: int = ENDS_S2_IN_S1,
@@ -904,20 +845,8 @@ def score_batch_semi(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, en
     by `mat` and the end gaps of `ends` (ENDS_* bits) free.  Returns a LOCAL_HIT_DTYPE array
     as score_batch_local does: score (it may be negative), end_i, end_j (the first row-major
     maximum among the admissible end cells) and begin_i = begin_j = -1."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    mat.check(s1, s2)
-    n = len(pairs)
-    hits = np.zeros(max(n, 1), LOCAL_HIT_DTYPE)
-    stats = NwBatchStats()
-    p = params((1, 0, int(gap)), waves, device)
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_score_batch_semi(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                                   off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
-                                   int(gap_open), int(ends), hits.ctypes.data_as(ctypes.POINTER(NwLocalHit)),
-                                   ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_score_batch_semi")
-    return (hits[:n], stats) if return_stats else hits[:n]
+    return _score_batch_call("nw_score_batch_semi", pairs, params((1, 0, int(gap)), waves, device),
+                             (int(gap_open), int(ends)), mat, hits=True, return_stats=return_stats)
 
 
 def align_batch_semi(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, ends: int = ENDS_S2_IN_S1,
@@ -925,27 +854,8 @@ def align_batch_semi(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, en
     """Batched semi-global alignments (nw_align_batch_semi): (hits, [ops of pair 0, ..],
     NwBatchStats), as align_batch_local returns them.  A pair's ops (0 diag, 1 up, 2 left)
     lead from its begin cell to its end cell; the skipped ends emit nothing."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    mat.check(s1, s2)
-    n = len(pairs)
-    ops_off = off1 + off2
-    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
-    hits = np.zeros(max(n, 1), LOCAL_HIT_DTYPE)
-    n_ops = np.zeros(max(n, 1), np.int64)
-    stats = NwBatchStats()
-    p = params((1, 0, int(gap)), waves, device)
-    o = NwBatchOpts(int(mem_bytes))
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_align_batch_semi(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                                   off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
-                                   int(gap_open), int(ends), ctypes.byref(o),
-                                   hits.ctypes.data_as(ctypes.POINTER(NwLocalHit)),
-                                   ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                   ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_align_batch_semi")
-    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
-    return hits[:n], out, stats
+    return _align_batch_call("nw_align_batch_semi", pairs, params((1, 0, int(gap)), waves, device), mem_bytes,
+                             (int(gap_open), int(ends)), mat, hits=True)
 
 
 def _band32(band) -> int:
@@ -967,20 +877,8 @@ def score_batch_banded(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, 
     and n2 = len(s2) rows, cell (i, j) counts iff min(0, n2 - n1) - band <= i - j <= max(0,
     n2 - n1) + band; the score is the best over the paths that stay inside.  A band of
     max(n1, n2) or more gives score_batch_matrix's scores."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    mat.check(s1, s2)
-    n = len(pairs)
-    scores = np.zeros(max(n, 1), np.int32)
-    stats = NwBatchStats()
-    p = params((1, 0, int(gap)), waves, device)
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_score_batch_banded(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                                     off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
-                                     int(gap_open), _band32(band), scores.ctypes.data_as(_i32p),
-                                     ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_score_batch_banded")
-    return (scores[:n], stats) if return_stats else scores[:n]
+    return _score_batch_call("nw_score_batch_banded", pairs, params((1, 0, int(gap)), waves, device),
+                             (int(gap_open), _band32(band)), mat, return_stats=return_stats)
 
 
 def align_batch_banded(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, band: int = 0, mem_bytes: int = 0,
@@ -988,26 +886,8 @@ def align_batch_banded(pairs, mat: SubMatrix, gap: int = -1, gap_open: int = 0, 
     """align_batch_matrix inside a band (nw_align_batch_banded): (scores, [ops of pair 0,
     ..], NwBatchStats).  Every vertex of a pair's path is in its band; direction bits are
     kept for the band's neighbourhood only (batch_banded_dir_bytes)."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    mat.check(s1, s2)
-    n = len(pairs)
-    ops_off = off1 + off2
-    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
-    scores = np.zeros(max(n, 1), np.int32)
-    n_ops = np.zeros(max(n, 1), np.int64)
-    stats = NwBatchStats()
-    p = params((1, 0, int(gap)), waves, device)
-    o = NwBatchOpts(int(mem_bytes))
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_align_batch_banded(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                                     off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
-                                     int(gap_open), _band32(band), ctypes.byref(o), scores.ctypes.data_as(_i32p),
-                                     ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                     ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_align_batch_banded")
-    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
-    return scores[:n], out, stats
+    return _align_batch_call("nw_align_batch_banded", pairs, params((1, 0, int(gap)), waves, device), mem_bytes,
+                             (int(gap_open), _band32(band)), mat)
 
 
 def batch_dual_dir_bytes(n1: int, n2: int) -> int:
@@ -1021,20 +901,8 @@ def score_batch_dual(pairs, mat: SubMatrix, gap: int = -2, gap_open: int = -4, g
     """score_batch_matrix under a two-piece gap cost (nw_score_batch_dual): a run of L ups
     or of L lefts costs max(gap_open + L * gap, gap_open2 + L * gap2) -- short indels by the
     steep piece, long ones by the flat piece.  Equal pieces give score_batch_matrix's scores."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    mat.check(s1, s2)
-    n = len(pairs)
-    scores = np.zeros(max(n, 1), np.int32)
-    stats = NwBatchStats()
-    p = params((1, 0, int(gap)), waves, device)
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_score_batch_dual(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                                   off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
-                                   int(gap_open), int(gap_open2), int(gap2), scores.ctypes.data_as(_i32p),
-                                   ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_score_batch_dual")
-    return (scores[:n], stats) if return_stats else scores[:n]
+    return _score_batch_call("nw_score_batch_dual", pairs, params((1, 0, int(gap)), waves, device),
+                             (int(gap_open), int(gap_open2), int(gap2)), mat, return_stats=return_stats)
 
 
 def align_batch_dual(pairs, mat: SubMatrix, gap: int = -2, gap_open: int = -4, gap2: int = -1, gap_open2: int = -24,
@@ -1042,26 +910,8 @@ def align_batch_dual(pairs, mat: SubMatrix, gap: int = -2, gap_open: int = -4, g
     """align_batch_matrix under a two-piece gap cost (nw_align_batch_dual): (scores, [ops of
     pair 0, ..], NwBatchStats).  The ops are 0 / 1 / 2 as everywhere: they do not say which
     piece priced a run (ops_score_dual takes the better one per run)."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    mat.check(s1, s2)
-    n = len(pairs)
-    ops_off = off1 + off2
-    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
-    scores = np.zeros(max(n, 1), np.int32)
-    n_ops = np.zeros(max(n, 1), np.int64)
-    stats = NwBatchStats()
-    p = params((1, 0, int(gap)), waves, device)
-    o = NwBatchOpts(int(mem_bytes))
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_align_batch_dual(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p), s2.ctypes.data_as(_i8p),
-                                   off2.ctypes.data_as(i64p), n, ctypes.byref(p), ctypes.byref(mat.c),
-                                   int(gap_open), int(gap_open2), int(gap2), ctypes.byref(o),
-                                   scores.ctypes.data_as(_i32p), ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                   ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p), ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_align_batch_dual")
-    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
-    return scores[:n], out, stats
+    return _align_batch_call("nw_align_batch_dual", pairs, params((1, 0, int(gap)), waves, device), mem_bytes,
+                             (int(gap_open), int(gap_open2), int(gap2)), mat)
 
 
 def batch_dual_banded_dir_bytes(n1: int, n2: int, band: int) -> int:
@@ -1078,20 +928,9 @@ def score_batch_dual_banded(pairs, mat: SubMatrix, gap: int = -2, gap_open: int 
     """score_batch_dual inside a band (nw_score_batch_dual_banded): only paths that stay within
     `band` diagonals of the pair's own (of 0 .. n2 - n1) count.  A covering band gives
     score_batch_dual's scores, equal pieces give score_batch_banded's."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    mat.check(s1, s2)
-    n = len(pairs)
-    scores = np.zeros(max(n, 1), np.int32)
-    stats = NwBatchStats()
-    p = params((1, 0, int(gap)), waves, device)
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_score_batch_dual_banded(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p),
-                                          s2.ctypes.data_as(_i8p), off2.ctypes.data_as(i64p), n, ctypes.byref(p),
-                                          ctypes.byref(mat.c), int(gap_open), int(gap_open2), int(gap2),
-                                          _band32(band), scores.ctypes.data_as(_i32p), ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_score_batch_dual_banded")
-    return (scores[:n], stats) if return_stats else scores[:n]
+    return _score_batch_call("nw_score_batch_dual_banded", pairs, params((1, 0, int(gap)), waves, device),
+                             (int(gap_open), int(gap_open2), int(gap2), _band32(band)), mat,
+                             return_stats=return_stats)
 
 
 def align_batch_dual_banded(pairs, mat: SubMatrix, gap: int = -2, gap_open: int = -4, gap2: int = -1,
@@ -1100,28 +939,8 @@ def align_batch_dual_banded(pairs, mat: SubMatrix, gap: int = -2, gap_open: int 
     """align_batch_dual inside a band (nw_align_batch_dual_banded): (scores, [ops of pair 0, ..],
     NwBatchStats); every vertex of a path lies in the band.  stats.dir_bytes counts the
     iterations of each strip's range alone (batch_dual_banded_dir_bytes)."""
-    s1, off1, s2, off2 = batch_csr(pairs)
-    mat.check(s1, s2)
-    n = len(pairs)
-    ops_off = off1 + off2
-    ops = np.zeros(max(int(ops_off[-1]), 1), np.uint8)
-    scores = np.zeros(max(n, 1), np.int32)
-    n_ops = np.zeros(max(n, 1), np.int64)
-    stats = NwBatchStats()
-    p = params((1, 0, int(gap)), waves, device)
-    o = NwBatchOpts(int(mem_bytes))
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    st = lib().nw_align_batch_dual_banded(s1.ctypes.data_as(_i8p), off1.ctypes.data_as(i64p),
-                                          s2.ctypes.data_as(_i8p), off2.ctypes.data_as(i64p), n, ctypes.byref(p),
-                                          ctypes.byref(mat.c), int(gap_open), int(gap_open2), int(gap2),
-                                          _band32(band), ctypes.byref(o), scores.ctypes.data_as(_i32p),
-                                          ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                          ops_off.ctypes.data_as(i64p), n_ops.ctypes.data_as(i64p),
-                                          ctypes.byref(stats))
-    if st != NW_OK:
-        raise NwError(st, "nw_align_batch_dual_banded")
-    out = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
-    return scores[:n], out, stats
+    return _align_batch_call("nw_align_batch_dual_banded", pairs, params((1, 0, int(gap)), waves, device), mem_bytes,
+                             (int(gap_open), int(gap_open2), int(gap2), _band32(band)), mat)
 
 
 def ops_score_dual(s1, s2, ops, mat: SubMatrix, gap: int = -2, gap_open: int = -4, gap2: int = -1,
@@ -1708,6 +1527,27 @@ class Context:
         band (an int, with mat): inside a band, see Context.score_batch_banded.
         piece2 ((gap_open2, gap2), with mat): two-piece gap cost, see Context.score_batch_dual;
         with band as well: inside a band, see Context.score_batch_dual_banded."""
+        m = () if mat is None else (ctypes.byref(mat.c), int(gap_open or 0))
+        if mat is not None and piece2 is not None and band is not None:
+            what, extra = "nw_score_batch_dual_banded_async", (*m, int(piece2[0]), int(piece2[1]), _band32(band))
+        elif mat is not None and piece2 is not None:
+            what, extra = "nw_score_batch_dual_async", (*m, int(piece2[0]), int(piece2[1]))
+        elif mat is not None and band is not None:
+            what, extra = "nw_score_batch_banded_async", (*m, _band32(band))
+        elif mat is not None:
+            what, extra = "nw_score_batch_matrix_async", m
+        elif gap_open is None:
+            what, extra = "nw_score_batch_async", ()
+        else:
+            what, extra = "nw_score_batch_affine_async", (int(gap_open),)
+        return self._score_batch_async(what, d_s1cat, d_off1, d_s2cat, d_off2, max_n2,
+                                       params(scheme, waves, self.device, flags), extra, stream)
+
+    def _score_batch_async(self, entry: str, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, p: NwParams, extra,
+                           stream, hits: bool = False):
+        """One asynchronous score call: the C entry `entry` on the device tensors under `p`, with
+        `extra` between the params and the results.  Returns the int32 CUDA tensor of npairs
+        scores, or with `hits` of (npairs, 8) words in nw_local_hit's layout."""
         import torch
         npairs = int(d_off1.numel()) - 1
         assert d_off1.dtype == torch.int64 and d_off2.dtype == torch.int64 and int(d_off2.numel()) == npairs + 1
@@ -1716,33 +1556,16 @@ class Context:
         if stream is None:
             stream = torch.cuda.current_stream(d_off1.device)
         with torch.cuda.stream(stream):
-            scores = torch.zeros(max(npairs, 1), dtype=torch.int32, device=d_off1.device)
-        p = params(scheme, waves, self.device, flags)
-        head = (self._h, ctypes.c_void_p(d_s1cat.data_ptr() if t1 else 0), ctypes.c_void_p(d_off1.data_ptr()),
-                ctypes.c_void_p(d_s2cat.data_ptr() if t2 else 0), ctypes.c_void_p(d_off2.data_ptr()), npairs, t1, t2,
-                int(max_n2), ctypes.byref(p))
-        tail = (ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(stream.cuda_stream))
-        if mat is not None and piece2 is not None and band is not None:
-            st, what = lib().nw_score_batch_dual_banded_async(*head, ctypes.byref(mat.c), int(gap_open or 0),
-                                                              int(piece2[0]), int(piece2[1]), _band32(band), *tail), \
-                "nw_score_batch_dual_banded_async"
-        elif mat is not None and piece2 is not None:
-            st, what = lib().nw_score_batch_dual_async(*head, ctypes.byref(mat.c), int(gap_open or 0),
-                                                       int(piece2[0]), int(piece2[1]), *tail), \
-                "nw_score_batch_dual_async"
-        elif mat is not None and band is not None:
-            st, what = lib().nw_score_batch_banded_async(*head, ctypes.byref(mat.c), int(gap_open or 0),
-                                                         _band32(band), *tail), "nw_score_batch_banded_async"
-        elif mat is not None:
-            st, what = lib().nw_score_batch_matrix_async(*head, ctypes.byref(mat.c), int(gap_open or 0), *tail), \
-                "nw_score_batch_matrix_async"
-        elif gap_open is None:
-            st, what = lib().nw_score_batch_async(*head, *tail), "nw_score_batch_async"
-        else:
-            st, what = lib().nw_score_batch_affine_async(*head, int(gap_open), *tail), "nw_score_batch_affine_async"
+            res = torch.zeros((max(npairs, 1), 8) if hits else max(npairs, 1), dtype=torch.int32,
+                              device=d_off1.device)
+        st = getattr(lib(), entry)(
+            self._h, ctypes.c_void_p(d_s1cat.data_ptr() if t1 else 0), ctypes.c_void_p(d_off1.data_ptr()),
+            ctypes.c_void_p(d_s2cat.data_ptr() if t2 else 0), ctypes.c_void_p(d_off2.data_ptr()), npairs, t1, t2,
+            int(max_n2), ctypes.byref(p), *extra, ctypes.c_void_p(res.data_ptr()),
+            ctypes.c_void_p(stream.cuda_stream))
         if st != NW_OK:
-            raise NwError(st, what)
-        return scores[:npairs]
+            raise NwError(st, entry)
+        return res[:npairs]
 
     def score_batch_affine(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, scheme=(1, 0, -1), gap_open: int = 0,
                            stream=None, waves: int = 0, flags: int = 0):
@@ -1756,8 +1579,7 @@ class Context:
         """score_batch_affine with substitution by matrix (nw_score_batch_matrix_async).  The
         sequences stay on the device and are not looked at: the matrix must name the
         letter unlisted bytes map to (SubMatrix(.., other=))."""
-        if mat.other is None and not mat.listed.all():
-            raise ValueError("Context.score_batch_matrix needs a matrix with other= (it cannot check the sequences)")
+        _needs_other(mat, "Context.score_batch_matrix")
         return self.score_batch(d_s1cat, d_off1, d_s2cat, d_off2, max_n2, (1, 0, int(gap)), stream, waves, 0,
                                 gap_open=int(gap_open), mat=mat)
 
@@ -1765,8 +1587,7 @@ class Context:
                            gap_open: int = 0, band: int = 0, stream=None, waves: int = 0):
         """Context.score_batch_matrix inside a band of `band` diagonals round each pair's own
         (nw_score_batch_banded_async, score_batch_banded)."""
-        if mat.other is None and not mat.listed.all():
-            raise ValueError("Context.score_batch_banded needs a matrix with other= (it cannot check the sequences)")
+        _needs_other(mat, "Context.score_batch_banded")
         return self.score_batch(d_s1cat, d_off1, d_s2cat, d_off2, max_n2, (1, 0, int(gap)), stream, waves, 0,
                                 gap_open=int(gap_open), mat=mat, band=int(band))
 
@@ -1774,8 +1595,7 @@ class Context:
                          gap_open: int = -4, gap2: int = -1, gap_open2: int = -24, stream=None, waves: int = 0):
         """Context.score_batch_matrix under the two-piece gap cost max(gap_open + L * gap,
         gap_open2 + L * gap2) per run of L (nw_score_batch_dual_async, score_batch_dual)."""
-        if mat.other is None and not mat.listed.all():
-            raise ValueError("Context.score_batch_dual needs a matrix with other= (it cannot check the sequences)")
+        _needs_other(mat, "Context.score_batch_dual")
         return self.score_batch(d_s1cat, d_off1, d_s2cat, d_off2, max_n2, (1, 0, int(gap)), stream, waves, 0,
                                 gap_open=int(gap_open), mat=mat, piece2=(int(gap_open2), int(gap2)))
 
@@ -1784,9 +1604,7 @@ class Context:
                                 stream=None, waves: int = 0):
         """Context.score_batch_dual inside a band of `band` diagonals round each pair's own
         (nw_score_batch_dual_banded_async, score_batch_dual_banded)."""
-        if mat.other is None and not mat.listed.all():
-            raise ValueError("Context.score_batch_dual_banded needs a matrix with other= (it cannot check the "
-                             "sequences)")
+        _needs_other(mat, "Context.score_batch_dual_banded")
         return self.score_batch(d_s1cat, d_off1, d_s2cat, d_off2, max_n2, (1, 0, int(gap)), stream, waves, 0,
                                 gap_open=int(gap_open), mat=mat, band=int(band),
                                 piece2=(int(gap_open2), int(gap2)))
@@ -1798,26 +1616,10 @@ class Context:
         8), a row in nw_local_hit's layout: score, end_i, end_j, begin_i = begin_j = -1,
         three zeros; a pair longer than max_n2: INT32_MIN and -1 in the four coordinates.
         Ordered on `stream`; nothing is synchronised."""
-        import torch
-        if mat.other is None and not mat.listed.all():
-            raise ValueError("Context.score_batch_local needs a matrix with other= (it cannot check the sequences)")
-        npairs = int(d_off1.numel()) - 1
-        assert d_off1.dtype == torch.int64 and d_off2.dtype == torch.int64 and int(d_off2.numel()) == npairs + 1
-        assert d_off1.is_contiguous() and d_off2.is_contiguous()
-        t1, t2 = int(d_s1cat.numel()), int(d_s2cat.numel())
-        if stream is None:
-            stream = torch.cuda.current_stream(d_off1.device)
-        with torch.cuda.stream(stream):
-            hits = torch.zeros((max(npairs, 1), 8), dtype=torch.int32, device=d_off1.device)
-        p = params((1, 0, int(gap)), waves, self.device, mode=MODE_SW)
-        st = lib().nw_score_batch_local_async(
-            self._h, ctypes.c_void_p(d_s1cat.data_ptr() if t1 else 0), ctypes.c_void_p(d_off1.data_ptr()),
-            ctypes.c_void_p(d_s2cat.data_ptr() if t2 else 0), ctypes.c_void_p(d_off2.data_ptr()), npairs, t1, t2,
-            int(max_n2), ctypes.byref(p), ctypes.byref(mat.c), int(gap_open), ctypes.c_void_p(hits.data_ptr()),
-            ctypes.c_void_p(stream.cuda_stream))
-        if st != NW_OK:
-            raise NwError(st, "nw_score_batch_local_async")
-        return hits[:npairs]
+        _needs_other(mat, "Context.score_batch_local")
+        return self._score_batch_async("nw_score_batch_local_async", d_s1cat, d_off1, d_s2cat, d_off2, max_n2,
+                                       params((1, 0, int(gap)), waves, self.device, mode=MODE_SW),
+                                       (ctypes.byref(mat.c), int(gap_open)), stream, hits=True)
 
     def score_batch_semi(self, d_s1cat, d_off1, d_s2cat, d_off2, max_n2: int, mat: SubMatrix, gap: int = -1,
                          gap_open: int = 0, ends: int = ENDS_S2_IN_S1, stream=None, waves: int = 0):
@@ -1826,26 +1628,10 @@ class Context:
         CUDA tensor (npairs, 8) in nw_local_hit's layout: score, end_i, end_j, begin_i =
         begin_j = -1, three zeros; a pair longer than max_n2: INT32_MIN and -1 in the four
         coordinates.  Ordered on `stream`; nothing is synchronised."""
-        import torch
-        if mat.other is None and not mat.listed.all():
-            raise ValueError("Context.score_batch_semi needs a matrix with other= (it cannot check the sequences)")
-        npairs = int(d_off1.numel()) - 1
-        assert d_off1.dtype == torch.int64 and d_off2.dtype == torch.int64 and int(d_off2.numel()) == npairs + 1
-        assert d_off1.is_contiguous() and d_off2.is_contiguous()
-        t1, t2 = int(d_s1cat.numel()), int(d_s2cat.numel())
-        if stream is None:
-            stream = torch.cuda.current_stream(d_off1.device)
-        with torch.cuda.stream(stream):
-            hits = torch.zeros((max(npairs, 1), 8), dtype=torch.int32, device=d_off1.device)
-        p = params((1, 0, int(gap)), waves, self.device)
-        st = lib().nw_score_batch_semi_async(
-            self._h, ctypes.c_void_p(d_s1cat.data_ptr() if t1 else 0), ctypes.c_void_p(d_off1.data_ptr()),
-            ctypes.c_void_p(d_s2cat.data_ptr() if t2 else 0), ctypes.c_void_p(d_off2.data_ptr()), npairs, t1, t2,
-            int(max_n2), ctypes.byref(p), ctypes.byref(mat.c), int(gap_open), int(ends),
-            ctypes.c_void_p(hits.data_ptr()), ctypes.c_void_p(stream.cuda_stream))
-        if st != NW_OK:
-            raise NwError(st, "nw_score_batch_semi_async")
-        return hits[:npairs]
+        _needs_other(mat, "Context.score_batch_semi")
+        return self._score_batch_async("nw_score_batch_semi_async", d_s1cat, d_off1, d_s2cat, d_off2, max_n2,
+                                       params((1, 0, int(gap)), waves, self.device),
+                                       (ctypes.byref(mat.c), int(gap_open), int(ends)), stream, hits=True)
 
     def traceback_block(self, d_s1, d_s2_block, table, row0: int, scheme=(1, 0, -1), stream=None, band: int = 0,
                         max_windows: int = 0, no_aim: bool = False):
