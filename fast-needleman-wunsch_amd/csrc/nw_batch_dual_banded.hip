@@ -35,6 +35,11 @@
 //   sees max(-2^29, -2^29 + go2) + dge = -2^29 + dge: ONE addition to the forced value, as in
 //   nw_batch_dual.hip, |dge| < 2^13.  Its right (lower) neighbour takes the maximum with H' +
 //   go2 of an in-band cell, a real value above -2^28, and the forced value is gone.
+//   (How much the forcing of E2' and F2' buys: the range bound has 2 A (n1 + n2 + 2) < 2^28 with
+//   |dge| <= 2 A, so an unforced chain drifts by less than 2^28 in all and stays below -2^28,
+//   under every real value, and above the int32 floor.  Within the accepted range it is margin:
+//   the sweep without it gives the same scores and ops on every test, DESIGN 6s.  It keeps the
+//   statement "added to at most once" true without an appeal to the pair's size.)
 //   Leaks.  What the in-band cells leak outward is a finite E1' right of the band (above it)
 //   and a finite F1' below it; E2' and F2' leak nothing, they are forced where they arrive.
 //   E1' moves right, away from the band, F1' down, away from it; the cells they reach have

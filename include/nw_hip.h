@@ -631,6 +631,11 @@ int nw_align_batch_local(const int8_t *s1cat, const int64_t *off1, const int8_t 
  * path; it may be negative.  As a table: the matrix entries' recurrence, no floor,
  *   E, F and H of inner cells as there;  E[i][0] = F[0][j] = -inf;  H[0][0] = 0;
  *   a boundary that is not free holds go + k * ge, a free one 0.
+ * The table is the definition.  With gap <= 0 it is the best score over those paths.  With
+ * gap > 0 a run along a free boundary from (0, 0) would be PAID go + k * ge > 0, and a free
+ * boundary holds 0 all the same: a skipped end is not priced, also where pricing it would
+ * gain, so the score may then be below the best path's (with ends = 0 nothing is free and the
+ * two agree for every gap).
  * End cell: among the admissible end cells of maximal H the first in row-major order
  * (smallest i, then smallest j), the local entries' rule; (n2, 0) and (0, n1) are
  * candidates where their side is free, so with ends = 15 the score is >= 0.
