@@ -7,10 +7,12 @@
 // One HostPath per device, created on first use and kept: the context, the
 // device table and sequence buffers (grow-only: a caller looping over pairs pays
 // no hipMalloc / hipFree of the table per call), a non-blocking copy stream and
-// two pinned staging chunks.  The table comes back to the caller's (pageable)
+// three pinned staging chunks.  The table comes back to the caller's (pageable)
 // buffer through the staging chunks: DMA of chunk k+1 overlaps the threaded
 // memcpy of chunk k into the caller's rows (tools/d2h_bench.cpp measured the
-// alternatives; DESIGN.md "drop-in path").  nw_host_release frees it all.
+// alternatives; DESIGN.md "drop-in path").  The chunk plan, the thread count and
+// the threaded memcpy are csrc/nw_hostcopy.h (no HIP: a CPU program can run them).
+// nw_host_release frees it all.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -19,6 +21,7 @@
 #include <vector>
 
 #include "nw_host_int.h"
+#include "nw_hostcopy.h"
 
 using namespace nwh;
 
@@ -32,18 +35,12 @@ struct HostPath {
     size_t tab_cap = 0;
     int8_t *s1 = nullptr, *s2 = nullptr;
     size_t s1_cap = 0, s2_cap = 0;
-    char *stage[3] = {nullptr, nullptr, nullptr};
-    size_t stage_cap = 0;  // bytes per staging chunk
+    char *stage[kStages] = {nullptr, nullptr, nullptr};
+    size_t stage_cap = 0;  // bytes per staging chunk (grow-only: nw_hostcopy.h copy_plan)
     hipStream_t copy = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t ev[kStages] = {nullptr, nullptr, nullptr};
 };
-constexpr int kStages = 3;
 
-// staging chunk: up to 256 MiB (a third of the table, at least 16 MiB), pinned
-// with hipHostMallocCoherent (tools/d2h_bench.cpp on the box: 40 GB through 3 x
-// 256 MiB coherent chunks and 8 copy threads at 56.6 GB/s, the bare pinned
-// hipMemcpy2D's 56.4; 128 MiB default-flag chunks 45-53)
-constexpr size_t kStageMax = 256u << 20, kStageMin = 16u << 20;
 // tables up to this size stay cached between calls; a larger one is released
 // when its call returns (it would crowd out the caller's own device work)
 constexpr size_t kKeepTableBytes = 16ull << 30;
@@ -98,32 +95,12 @@ int host_prepare(HostPath &h, int dev, const int8_t *s1, int64_t n1, const int8_
     return NW_OK;
 }
 
-void par_memcpy(char *dst, const char *src, size_t bytes, int threads) {
-    if (threads <= 1 || bytes < (8u << 20)) {
-        std::memcpy(dst, src, bytes);
-        return;
-    }
-    std::vector<std::thread> ts;
-    const size_t per = (bytes / (size_t)threads + 4095) & ~(size_t)4095;
-    for (int t = 1; t < threads; ++t) {
-        const size_t o = (size_t)t * per;
-        if (o >= bytes) break;
-        ts.emplace_back([=] { std::memcpy(dst + o, src + o, std::min(per, bytes - o)); });
-    }
-    std::memcpy(dst, src, std::min(per, bytes));
-    for (auto &t : ts) t.join();
-}
-
-int copy_threads() {
-    if (env_set("NW_COPY_THREADS")) return std::max(1, env_int("NW_COPY_THREADS", 1));
-    return (int)std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency()));
-}
+int copy_threads() { return copy_threads_of(std::getenv("NW_COPY_THREADS"), std::thread::hardware_concurrency()); }
 
 // Rows 0..n2 (n1 + 1 int32 each) of the device table into host rows of
 // `stride` int32 (the reference layout: stride = n1 + 1), through the pinned
 // staging chunks.
-int host_staging(HostPath &h, size_t table_bytes) {
-    size_t want = std::min(kStageMax, std::max(kStageMin, (table_bytes / kStages + (2u << 20) - 1) & ~((size_t)(2u << 20) - 1)));
+int host_staging(HostPath &h, size_t want) {  // want: bytes per chunk (copy_plan, stage_want)
     if (want > h.stage_cap) {
         for (int k = 0; k < kStages; ++k) {
             if (h.stage[k]) (void)hipHostFree(h.stage[k]);
@@ -145,17 +122,17 @@ int host_copy_back(HostPath &h, const int32_t *d_t, int64_t pitch, int64_t n1, i
     int st;
     const size_t w = (size_t)(n1 + 1) * 4;
     const int64_t rows = n2 + 1;
-    if ((st = host_staging(h, w * (size_t)rows)) != NW_OK) return st;
-    const int64_t rpc = std::max<int64_t>(1, (int64_t)(h.stage_cap / w));
-    if ((size_t)rpc * w > h.stage_cap) {  // one row wider than a chunk: direct
+    const CopyPlan plan = copy_plan(w * (size_t)rows, w, rows, h.stage_cap);
+    if ((st = host_staging(h, plan.stage_cap)) != NW_OK) return st;
+    if (plan.direct) {  // one row wider than a chunk
         NW_HIP_TRY(hipMemcpy2D(host, (size_t)stride * 4, d_t, (size_t)pitch * 4, w, (size_t)rows,
                                hipMemcpyDeviceToHost));
         return NW_OK;
     }
-    const int64_t nch = (rows + rpc - 1) / rpc;
+    const int64_t nch = plan.nch;
     const int threads = copy_threads();
     auto issue = [&](int64_t ch) -> hipError_t {
-        const int64_t r0 = ch * rpc, nr = std::min(rpc, rows - r0);
+        const int64_t r0 = plan.first_row(ch), nr = plan.rows_of(ch, rows);
         hipError_t e = hipMemcpy2DAsync(h.stage[ch % kStages], w, d_t + r0 * pitch, (size_t)pitch * 4, w,
                                         (size_t)nr, hipMemcpyDeviceToHost, h.copy);
         return e == hipSuccess ? hipEventRecord(h.ev[ch % kStages], h.copy) : e;
@@ -170,7 +147,7 @@ int host_copy_back(HostPath &h, const int32_t *d_t, int64_t pitch, int64_t n1, i
         NW_HIP_TRY(hipEventSynchronize(h.ev[ch % kStages]));
         const auto a1 = tnow();
         t_dma += sec(a0, a1);
-        const int64_t r0 = ch * rpc, nr = std::min(rpc, rows - r0);
+        const int64_t r0 = plan.first_row(ch), nr = plan.rows_of(ch, rows);
         const char *src = h.stage[ch % kStages];
         if (stride * 4 == (int64_t)w) {
             par_memcpy((char *)(host + r0 * stride), src, (size_t)nr * w, threads);
@@ -263,7 +240,7 @@ int nw_host_warmup(int device) {
     std::lock_guard<std::mutex> lock(h.mu);
     if (!h.c && (st = nw_ctx_create(dev, &h.c)) != NW_OK) return st;
     NW_HIP_TRY(hipSetDevice(dev));
-    return host_staging(h, kStageMax * kStages);
+    return host_staging(h, stage_want(kStageMax * kStages));
 }
 
 void nw_host_release(int device) {

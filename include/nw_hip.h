@@ -164,7 +164,11 @@ int nw_fill(const int8_t *s1, int64_t n1, const int8_t *s2, int64_t n2,
  * context, the device table (kept when at most 16 GiB) and sequence buffers,
  * and three pinned staging chunks (up to 256 MiB each) through which the
  * table is copied back (DMA of the next chunks overlapping the threaded copy of
- * one into host_t; NW_COPY_THREADS sets the copy threads, default min(8, cores)).
+ * one into host_t; NW_COPY_THREADS sets the copy threads, default min(8, cores):
+ * it is read on every call and clamped to 1..64 -- 0, a negative or a
+ * non-numeric value is 1, anything above 64 is 64; a chunk below 8 MiB is one
+ * memcpy whatever the count).  The chunks only grow, so how a table is cut
+ * depends on the largest table since the last nw_host_release.
  * nw_host_warmup(device) creates it ahead of the first call (context, copy
  * stream, staging; not the table, whose size is not known yet; -1: the current
  * device); nw_host_release(device) frees it (-1: every device).
